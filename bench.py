@@ -7,11 +7,17 @@ forward + backward) and one full sliding-window BA solve of config 3 (10 keyfram
 2000 landmarks per GPU, 24,000 observations per GPU, LM to convergence, <= 20 iterations) --
 every frame is treated as a keyframe (worst case of estimator.rs:243-246).
 
-`value` is BASELINE.md's protocol step, the median of --reps repetitions: the two images go up
-from pinned host memory, the three tracked feature lists come back, a NEW keyframe window is
-uploaded (rsvio_ba_set_problem; two pre-built windows alternate) and solved, and its optimised
-state comes back -- all inside the timed region.  `value_resident` is the device-resident step
-(images and the window already in HBM, the same window re-solved from its captured graph).
+`value` is BASELINE.md's protocol step: the two images go up from pinned host memory, the three
+tracked feature lists come back, a NEW keyframe window is uploaded (rsvio_ba_set_problem; two
+pre-built windows alternate) and solved, and its optimised state comes back -- all inside the
+timed region.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only that: it sets up, runs W
+protocol steps untimed, times N of them (`ms_per_step` = that time / N), writes the last step's
+outputs with --dump-outputs DIR, and prints the result line.  Everything else is behind --full:
+5 repetitions of the N steps (`value` = their median), `value_resident` (the device-resident
+step: images and the window already in HBM, the same window re-solved from its captured graph),
+the rows and the CPU baselines below.
 
 Multi-GPU (torchrun, one process per GPU): the tracker runs as independent replicas (each rank
 its own stream); the BA is ONE problem whose landmarks are sharded 2000 per rank (weak scaling)
@@ -19,7 +25,8 @@ with an RCCL all-reduce of the reduced camera system per LM iteration.  value = 
 ranks / max-over-ranks time.
 
 Also reported: BA ms per LM iteration, tracker ms per frame, the dominant kernel's roofline
-(HIP events on the stream it runs on) and the CPU oracle baseline on the host cores (rank 0).
+(HIP events on the stream it runs on, sampled inside the timed steps) and, with --full, the CPU
+oracle baseline on the host cores (rank 0).
 """
 from __future__ import annotations
 
@@ -48,6 +55,34 @@ FP64_PEAK_TFLOPS = 78.6            # MI355X FP64 vector (spec)
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def rnd(x, n):
+    """round(x, n); None for a figure that was not measured (None or NaN)."""
+    return None if x is None or math.isnan(x) else round(x, n)
+
+
+def dump_outputs(directory, trk, state_out, ba_iterations):
+    """--dump-outputs: what the last timed protocol step handed back to its caller, one .npy per
+    array (under 200 KB in all).  The inputs are seeded and the step that is last depends only on
+    --steps, --warmup and --reps, so two builds run with the same arguments can be compared
+    array by array:
+      tracker_valid     (3, 300)    float32  1 = tracked; the batches are cam0 temporal, cam1
+                                             temporal, cam0 -> cam1 stereo
+      tracker_features  (3, 300, 6) float32  the tracked feature states (2x2 affine, x, y); rows
+                                             whose flag is 0 carry no result and are written as 0
+      ba_poses          (10, 7)     float64  the solved window's keyframe poses
+      ba_landmarks      (n_lm, 3)   float64  its landmarks
+      ba_iterations     (1,)        float64  the LM iterations the solve took"""
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    valid = trk.h_valid.numpy() != 0
+    feats = np.where(valid[:, :, None], trk.h_out.numpy(), np.float32(0))
+    np.save(d / "tracker_valid.npy", valid.astype(np.float32))
+    np.save(d / "tracker_features.npy", feats.astype(np.float32))
+    np.save(d / "ba_poses.npy", np.asarray(state_out[0], np.float64))
+    np.save(d / "ba_landmarks.npy", np.asarray(state_out[1], np.float64))
+    np.save(d / "ba_iterations.npy", np.array([ba_iterations], np.float64))
 
 
 # ---------------------------------------------------------------------------------------
@@ -1450,14 +1485,26 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--reps", type=int, default=5, help="timed repetitions of --steps steps; value = median")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline sample budget (rank 0, N=1)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-rows", action="store_true", help="skip the unprojection / track_motion row measurements")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="timed repetitions of --steps steps each; value = their median (default 1: --steps is the "
+                         "number of timed steps; 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: 5 repetitions by default, the device-resident step, the "
+                         "rows (unprojection, track_motion, config 5, batched BA and tracker, feature_tracker, the "
+                         "config-4 Estimator with its oracle parity check) and the CPU baselines.  Without it the "
+                         "run sets up, warms up, times --steps protocol steps and prints the result line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed protocol step returned to its caller as "
+                         "DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0,
+                    help="--full: CPU baseline sample budget (rank 0, N=1)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baselines and the oracle legs")
+    ap.add_argument("--no-rows", action="store_true",
+                    help="--full without the unprojection / track_motion row measurements")
     ap.add_argument("--pipeline-frames", type=int, default=500,
-                    help="config-4 Estimator row: rendered frames (0: skip)")
+                    help="--full: config-4 Estimator row: rendered frames (0: skip)")
     ap.add_argument("--batch-streams", type=int, default=64,
-                    help="batched tracker row: independent stereo streams per launch (0: skip)")
+                    help="--full: batched tracker row: independent stereo streams per launch (0: skip)")
     ap.add_argument("--cu-split", type=float, default=0.25,
                     help="fraction of CUs given to the tracker stream (0: no CU partition); 0.25 measured "
                          "best (round 2 sweep: K4c's 360 two-wave-per-SIMD workgroups fit the BA's 192 CUs "
@@ -1510,6 +1557,12 @@ def main():
     ap.add_argument("--same-device", action="store_true",
                     help="rehearsal on a one-GPU box: all ranks on cuda:0, gloo control group, P2P exchange")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.reps is None:
+        args.reps = 5 if args.full else 1
+    if args.reps < 1:
+        ap.error("--reps must be at least 1")
     if args.same_device:
         args.collective = "p2p"
         # (ranks sharing one GPU never take the iterations whose next decision waits in K4c,
@@ -1619,31 +1672,36 @@ def main():
             gc.enable()
         return out
 
-    if args.precapture_graphs:
-        trk.precapture(False, False)
-    for _ in range(args.warmup):
-        resident_step(False)
-    el_res = timed_reps(resident_step, args.reps)
-    lk_ms_resident = trk.lk_ms()
-    trk.ev.clear()
-    ba_iters_res, ba_solve_ms_res = float(np.mean(ba.iters)), float(np.mean(ba.solve_ms))
-    ba.iters.clear()
-    ba.solve_ms.clear()
+    el_res = None
+    if args.full:  # the device-resident step, measured before the protocol step
+        if args.precapture_graphs:
+            trk.precapture(False, False)
+        for _ in range(args.warmup):
+            resident_step(False)
+        el_res = timed_reps(resident_step, args.reps)
+        lk_ms_resident = trk.lk_ms()
+        trk.ev.clear()
+        ba_iters_res, ba_solve_ms_res = float(np.mean(ba.iters)), float(np.mean(ba.solve_ms))
+        ba.iters.clear()
+        ba.solve_ms.clear()
     trk.enable_pcie()
     if args.pin_windows:
         ba.pin_windows()
     if args.precapture_graphs:
         trk.precapture(True, args.order in ("split", "window-first"))
     native = None
+    # warm-up: --warmup protocol steps (--full: at least 2, as it always ran them)
+    n_warm = max(args.warmup, 2) if args.full else args.warmup
     if args.driver == "native" and args.order in ("split", "window-first"):
-        native = NativeProtocol(trk, ba, state_out, max(args.steps, args.warmup, 2),
+        native = NativeProtocol(trk, ba, state_out, max(args.steps, n_warm, 2),
                                 order=1 if args.order == "window-first" else 0)
-        native.run(max(args.warmup, 2))
+        if n_warm:
+            native.run(n_warm)
         if trace is not None:
             native.phases = []
             native.timeline = []
     else:
-        for _ in range(max(args.warmup, 2)):
+        for _ in range(n_warm):
             protocol_step(False)
     minflt0 = _minor_faults()
     if native is None:
@@ -1664,6 +1722,8 @@ def main():
             ba.solve_ms += sms
             lk_pro += lk
     minflt = _minor_faults() - minflt0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trk, state_out, ba.iters[-1])
     if native is not None and native.phases is not None:  # the native driver's own host phase times
         names = ["upload", "set_problem", "start", "frame_enqueue", "frame_wait", "solve_wait", "state"]
         ph = np.array(native.phases)
@@ -1686,19 +1746,19 @@ def main():
                        "thp": _read_text("/sys/kernel/mm/transparent_hugepage/enabled"),
                        "thp_defrag": _read_text("/sys/kernel/mm/transparent_hugepage/defrag")}, f)
     elapsed = float(np.median(el_pro))
-    elapsed_res = float(np.median(el_res))
 
     frames = world * args.steps
     value = frames / elapsed
-    value_res = frames / elapsed_res
+    # (the LK launch is sampled on every 4th frame: None when no timed step was one)
     lk_ms = trk.lk_ms() if lk_pro is None else (float(np.mean(lk_pro)) if lk_pro else float("nan"))
     ba_iters = float(np.mean(ba.iters))
     ba_solve_ms = float(np.mean(ba.solve_ms))
     ba_ms_iter = ba_solve_ms / ba_iters
-    ba_ms_iter_res = ba_solve_ms_res / ba_iters_res
     calls = 3 * NFEAT * 2
     lk_bytes = lk_bytes_per_launch(calls)
     achieved = lk_bytes / (lk_ms * 1e-3) / 1e9
+    if math.isnan(lk_ms):
+        lk_ms = achieved = None
     prob = ba.prob
     flops = ba_flops_per_iter(prob.n_obs, prob.n_lm, 6, int((prob.kf_fixed == 0).sum()))
     traffic, traffic_src = pmc_traffic("lk_track_kernel")
@@ -1726,11 +1786,6 @@ def main():
         "protocol_minor_faults": minflt,
         "host_numa_balancing": _read_text("/proc/sys/kernel/numa_balancing"),
         "value_reps_max": round(frames / min(el_pro), 3),
-        "value_resident": round(value_res, 3),
-        "ms_per_step_resident": round(1e3 * elapsed_res / args.steps, 4),
-        "value_resident_note": "inputs resident in HBM, the same window re-solved each step (its graph "
-                               "replayed), nothing crosses PCIe but the LM status reads",
-        "value_resident_reps": [round(frames / e, 3) for e in el_res],
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -1750,15 +1805,13 @@ def main():
         "ba_ms_per_iter": round(ba_ms_iter, 4),
         "ba_iterations": ba_iters,
         "ba_ms_per_solve": round(ba_solve_ms, 4),
-        "ba_ms_per_iter_resident": round(ba_ms_iter_res, 4),
-        "ba_ms_per_solve_resident": round(ba_solve_ms_res, 4),
-        "tracker_lk_ms_per_frame_resident": round(lk_ms_resident, 4),
-        "tracker_lk_ms_per_frame": round(lk_ms, 4),
-        "roofline": {"kernel": "lk_track_kernel", "bound": "hbm", "achieved": round(achieved, 2),
-                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
+        "tracker_lk_ms_per_frame": rnd(lk_ms, 4),
+        "roofline": {"kernel": "lk_track_kernel", "bound": "hbm", "achieved": rnd(achieved, 2),
+                     "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": rnd(achieved / HBM_PEAK_GBS, 6) if achieved is not None else None,
                      "traffic": None if traffic is None else round(traffic),
                      "traffic_detail": traffic_src,
-                     "algorithmic_bytes_per_launch": lk_bytes, "launch_ms": round(lk_ms, 4),
+                     "algorithmic_bytes_per_launch": lk_bytes, "launch_ms": rnd(lk_ms, 4),
                      "note": "the step's longest single kernel; latency-bound: 900 one-wave workgroups "
                              "(fwd+bwd chains) on the tracker's CUs",
                      "step_bound": {"by": "BA LM chain (K4c -> K5 -> K6 per iteration, one stream)",
@@ -1772,20 +1825,32 @@ def main():
                         "achieved_tflops": round(flops / (ba_ms_iter * 1e-3) / 1e12, 4),
                         "peak_tflops": FP64_PEAK_TFLOPS},
     }
+    if args.full:
+        elapsed_res = float(np.median(el_res))
+        out.update({
+            "value_resident": round(frames / elapsed_res, 3),
+            "ms_per_step_resident": round(1e3 * elapsed_res / args.steps, 4),
+            "value_resident_note": "inputs resident in HBM, the same window re-solved each step (its graph "
+                                   "replayed), nothing crosses PCIe but the LM status reads",
+            "value_resident_reps": [round(frames / e, 3) for e in el_res],
+            "ba_ms_per_iter_resident": round(ba_solve_ms_res / ba_iters_res, 4),
+            "ba_ms_per_solve_resident": round(ba_solve_ms_res, 4),
+            "tracker_lk_ms_per_frame_resident": rnd(lk_ms_resident, 4),
+        })
     if world > 1:
         out["ba_exchange"] = {"collective": ba.collective, "p2p_latency_us": ba.p2p_us,
                               "fold": os.environ.get("RSVIO_P2P_FOLD", "3") if ba.collective == "p2p" else None,
                               "flag_in_word_system": os.environ.get("RSVIO_P2P_LL", "0") == "1"
                               if ba.collective == "p2p" else None}
-    if rank == 0 and not args.no_rows:
+    if args.full and rank == 0 and not args.no_rows:
         out["rows"] = measure_rows(local, cpu=(world == 1 and not args.no_cpu))
-    if rank == 0 and not args.no_rows and args.batch_streams > 0:
+    if args.full and rank == 0 and not args.no_rows and args.batch_streams > 0:
         out.setdefault("rows", {})["tracker_batched"] = measure_tracker_batched_row(trk, local, args.batch_streams)
-    if rank == 0 and not args.no_rows and args.pipeline_frames > 0:
+    if args.full and rank == 0 and not args.no_rows and args.pipeline_frames > 0:
         out.setdefault("rows", {})["pipeline_config4"] = measure_pipeline_row(
             local, cpu=(world == 1 and not args.no_cpu), n_frames=args.pipeline_frames,
             native=args.driver == "native")
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         # two legs -- all host cores (the reported baseline, rayon's parallelism) and
         # one thread -- each a bounded sample of the same per-frame work
         cores = host_cores()

@@ -7,7 +7,7 @@ set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 TAG=$1; REF=$2; REPS=${3:-2}
-HEAD="bench.py --steps 20 --warmup 3 --no-cpu --no-rows --pipeline-frames 0"
+HEAD="bench.py --steps 20 --warmup 3 --full --no-cpu --no-rows --pipeline-frames 0"
 for rep in $(seq 1 $REPS); do
   for v in new ref; do
     if [ $v = ref ]; then L="RSVIO_LIB=$REF"; else L=""; fi

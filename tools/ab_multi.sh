@@ -8,7 +8,7 @@ set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 TAG=$1; REPS=$2; shift 2
-HEAD="bench.py --steps 20 --warmup 5 --no-cpu --no-rows --pipeline-frames 0"
+HEAD="bench.py --steps 20 --warmup 5 --full --no-cpu --no-rows --pipeline-frames 0"
 for rep in $(seq 1 $REPS); do
   for spec in "$@"; do
     name=${spec%%=*}; envs=${spec#*=}

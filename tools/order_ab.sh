@@ -4,7 +4,7 @@ set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 TAG=${1:-order}
-HEAD="bench.py --steps 20 --warmup 10 --reps 5 --no-cpu --no-rows --pipeline-frames 0"
+HEAD="bench.py --steps 20 --warmup 10 --reps 5 --full --no-cpu --no-rows --pipeline-frames 0"
 for cfg in "ba-first 0.25" "split 0.25" "ba-first 0.25" "split 0.25"; do
   set -- $cfg
   f=gpurun_out/head_${TAG}_$1_$2

@@ -9,7 +9,7 @@ timeout -k 10 700 python -u -m pytest tests/test_ba_gpu.py -x -v -m gpu --timeou
 tail -5 gpurun_out/r06a_tests8.log
 for i in 0 1 2; do
   pc=1; [ $i = 0 ] && pc=0
-  timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu --no-rows --pipeline-frames 0 --precapture-graphs $pc \
+  timeout -k 10 300 python bench.py --steps 20 --warmup 5 --reps 5 --no-cpu --no-rows --pipeline-frames 0 --precapture-graphs $pc \
     --trace-steps gpurun_out/r06a_trace$i.json > gpurun_out/r06a_bench$i.json 2> gpurun_out/r06a_bench$i.err || { tail -30 gpurun_out/r06a_bench$i.err; exit 1; }
   python -c "import json;d=json.load(open('gpurun_out/r06a_bench$i.json'));print($pc, d['value'],d['value_reps'])"
 done

@@ -3,14 +3,14 @@
 # with its rows (config-4 row on the native Estimator), no CPU legs
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out
+export OUT=${OUT:-bench_out}; mkdir -p $OUT
 timeout -k 10 600 python -u -m pytest tests/test_estimator_gpu.py -x -v -m gpu --timeout 300 --timeout-method thread \
-  -k "native or pipelined" > gpurun_out/r06k_est_tests.log 2>&1 || { tail -40 gpurun_out/r06k_est_tests.log; exit 1; }
-tail -3 gpurun_out/r06k_est_tests.log
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 --no-cpu --batch-streams 0 > gpurun_out/r06k_bench.json 2> gpurun_out/r06k_bench.err || { tail -30 gpurun_out/r06k_bench.err; exit 1; }
+  -k "native or pipelined" > $OUT/r06k_est_tests.log 2>&1 || { tail -40 $OUT/r06k_est_tests.log; exit 1; }
+tail -3 $OUT/r06k_est_tests.log
+timeout -k 10 400 python bench.py --steps 20 --warmup 5 --full --no-cpu --batch-streams 0 > $OUT/r06k_bench.json 2> $OUT/r06k_bench.err || { tail -30 $OUT/r06k_bench.err; exit 1; }
 python - <<'PY'
-import json
-d = json.load(open("gpurun_out/r06k_bench.json"))
+import json, os
+d = json.load(open(os.environ["OUT"] + "/r06k_bench.json"))
 print(d["value"], d["value_reps"], d["ba_ms_per_iter"], d["driver"])
 r = d["rows"]
 p = r["pipeline_config4"]

@@ -5,7 +5,7 @@
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
-B="python bench.py --steps 20 --warmup 5 --no-cpu --no-rows --pipeline-frames 0"
+B="python bench.py --steps 20 --warmup 5 --reps 5 --no-cpu --no-rows --pipeline-frames 0"
 show() { python -c "import json,sys;d=json.load(open(sys.argv[1]));print(sys.argv[2],d['value'],d['value_reps_min'],d['value_reps_max'],d['ba_ms_per_iter'],d['tracker_lk_ms_per_frame'],d.get('protocol_minor_faults'))" "$1" "$2"; }
 for rep in 1 2 3; do
   for t in 0 3; do

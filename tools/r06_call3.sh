@@ -11,7 +11,7 @@ timeout -k 10 120 python tools/pnp_probe.py > gpurun_out/r06c_pnp_stamps.txt 2>&
 cat gpurun_out/r06c_pnp_stamps.txt
 for i in 1 2 3 4 5 6; do
   pin=$((i % 2))
-  timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu --no-rows --pipeline-frames 0 --pin-windows $pin \
+  timeout -k 10 300 python bench.py --steps 20 --warmup 5 --reps 5 --no-cpu --no-rows --pipeline-frames 0 --pin-windows $pin \
     --trace-steps gpurun_out/r06c_trace$i.json > gpurun_out/r06c_bench$i.json 2> gpurun_out/r06c_bench$i.err || { tail -30 gpurun_out/r06c_bench$i.err; exit 1; }
   python -c "import json;d=json.load(open('gpurun_out/r06c_bench$i.json'));print('pin',$pin,d['value'],d['value_reps'],d['protocol_minor_faults'],d['host_numa_balancing'])"
 done

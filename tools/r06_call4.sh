@@ -21,7 +21,7 @@ RSVIO_LIB=rs-vio_amd/lib/librsvio_gpu_base.so timeout -k 10 120 python tools/pnp
 timeout -k 10 120 python tools/pnp_kernel_ms.py new >> gpurun_out/r06d_pnp_ab.txt 2>&1 || { cat gpurun_out/r06d_pnp_ab.txt; exit 1; }
 cat gpurun_out/r06d_pnp_ab.txt
 for i in 1 2 3; do
-  timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu --no-rows --pipeline-frames 0 \
+  timeout -k 10 300 python bench.py --steps 20 --warmup 5 --full --no-cpu --no-rows --pipeline-frames 0 \
     --trace-steps gpurun_out/r06d_trace$i.json > gpurun_out/r06d_bench$i.json 2> gpurun_out/r06d_bench$i.err || { tail -30 gpurun_out/r06d_bench$i.err; exit 1; }
   python -c "import json;d=json.load(open('gpurun_out/r06d_bench$i.json'));print(d['value'],d['value_reps'],d['ba_ms_per_iter'],d['ba_ms_per_iter_resident'],d['protocol_minor_faults'])"
 done

@@ -17,7 +17,7 @@ python3 tools/kstats.py gpurun_out/r06e_c5prof | head -9 | tee gpurun_out/r06e_c
 rm -f gpurun_out/r06e_c5prof/run_kernel_trace.csv
 for i in 1 2 3; do
   tr=""; [ $i = 3 ] && tr="--trace-steps gpurun_out/r06e_trace$i.json"
-  timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu --no-rows --pipeline-frames 0 $tr \
+  timeout -k 10 300 python bench.py --steps 20 --warmup 5 --full --no-cpu --no-rows --pipeline-frames 0 $tr \
     > gpurun_out/r06e_bench$i.json 2> gpurun_out/r06e_bench$i.err || { tail -30 gpurun_out/r06e_bench$i.err; exit 1; }
   python -c "import json;d=json.load(open('gpurun_out/r06e_bench$i.json'));print(d['value'],d['value_reps'],d['ba_ms_per_iter'],d['ba_ms_per_iter_resident'],d['protocol_minor_faults'])"
 done

@@ -19,7 +19,7 @@ rm -f gpurun_out/r06h_c5prof/run_kernel_trace.csv
 tools/ab_lib.sh r06h_rlq rs-vio_amd/lib/librsvio_gpu_rlq.so 3 || exit 1
 for rep in 1 2; do
   for ec in 1 0; do
-    RSVIO_BA_EARLY_COPY=$ec timeout -k 10 240 python bench.py --steps 20 --warmup 5 --no-cpu --no-rows --pipeline-frames 0 \
+    RSVIO_BA_EARLY_COPY=$ec timeout -k 10 240 python bench.py --steps 20 --warmup 5 --reps 5 --no-cpu --no-rows --pipeline-frames 0 \
       > gpurun_out/r06h_ec${ec}_$rep.json 2> gpurun_out/r06h_ec${ec}_$rep.err || { tail -20 gpurun_out/r06h_ec${ec}_$rep.err; exit 1; }
     python -c "import json;d=json.load(open('gpurun_out/r06h_ec${ec}_$rep.json'));print('early_copy',$ec,d['value'],d['value_reps'],d['ba_ms_per_iter'])"
   done

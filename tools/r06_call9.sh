@@ -10,7 +10,7 @@ tail -1 gpurun_out/r06i_ba_tests.log
 tools/ab_lib.sh r06i_rcp rs-vio_amd/lib/librsvio_gpu_rcplate.so 3 || exit 1
 for rep in 1 2 3 4; do
   for tm in 0 1; do
-    timeout -k 10 240 python bench.py --steps 20 --warmup 5 --no-cpu --no-rows --pipeline-frames 0 --tame-malloc $tm \
+    timeout -k 10 240 python bench.py --steps 20 --warmup 5 --reps 5 --no-cpu --no-rows --pipeline-frames 0 --tame-malloc $tm \
       > gpurun_out/r06i_tm${tm}_$rep.json 2> gpurun_out/r06i_tm${tm}_$rep.err || { tail -20 gpurun_out/r06i_tm${tm}_$rep.err; exit 1; }
     python -c "import json;d=json.load(open('gpurun_out/r06i_tm${tm}_$rep.json'));print('tame',$tm,d['value'],d['value_reps_min'],d['protocol_minor_faults'],d['ba_ms_per_iter'])"
   done
