@@ -24,6 +24,8 @@
 //                               and the speculative linearisation of the trial state (residual,
 //                               Jacobian, Huber) into the other raw buffers -- its cost is the
 //                               trial cost; an accepted step needs no further linearisation
+//       (the last K6 of a chunk, with the state export on: the current state into pinned host
+//        memory and the trial's cost only -- ba_backsub_trial_export, see k6_body)
 //   [sharded: K6r per-rank trial scalars + RCCL all-reduce, K7 ba_lm_decide]
 //   single rank: the last K6 wave to arrive takes the LM decision (gain ratio, accept / reject
 //   = buffer flip, lambda, termination)
@@ -227,7 +229,8 @@ struct Work {
     double* trial4;          // 4 (sharded: reduced trial scalars)
     const LmState* st_prev;  // K4c: the state left by the previous iteration (read only)
     LmState* st;             // this iteration's state (K4c's owner block writes it; K5, K6 use it)
-    unsigned long long* tick;  // [0] decisions published to the host, [1] solve start (wall clock)
+    unsigned long long* tick;  // [0] decisions published to the host, [1] solve start (wall clock),
+                               // [2] [3] the export of a chunk's last K6: its solve's stamp [1] and cur + 1
 };
 
 __device__ __forceinline__ size_t sys_len(const Geometry& G) { return (size_t)G.n_pb * 36 + 12 * G.n_free + 2; }
@@ -447,18 +450,23 @@ struct SlotLin {
     double V[6], gp[3], Wr[9], Ur[6], gr[3], cost;
 };
 
+// COST_ONLY (the last K6 of a chunk): the residual and its Huber cost alone, by the same
+// operations -- no Jacobian, and of L only cost is set
+template <bool COST_ONLY = false>
 __device__ __forceinline__ void slot_linearize(const Geometry& G, const Pose& P, const double p[3], int nobs,
                                                int cams, const double2 (&uvq)[2], bool fr, SlotLin& L) {
+    if constexpr (!COST_ONLY) {
 #pragma unroll
-    for (int i = 0; i < 6; ++i) L.V[i] = 0.0;
+        for (int i = 0; i < 6; ++i) L.V[i] = 0.0;
 #pragma unroll
-    for (int i = 0; i < 3; ++i) L.gp[i] = 0.0;
+        for (int i = 0; i < 3; ++i) L.gp[i] = 0.0;
 #pragma unroll
-    for (int i = 0; i < 9; ++i) L.Wr[i] = 0.0;
+        for (int i = 0; i < 9; ++i) L.Wr[i] = 0.0;
 #pragma unroll
-    for (int i = 0; i < 6; ++i) L.Ur[i] = 0.0;
+        for (int i = 0; i < 6; ++i) L.Ur[i] = 0.0;
 #pragma unroll
-    for (int i = 0; i < 3; ++i) L.gr[i] = 0.0;
+        for (int i = 0; i < 3; ++i) L.gr[i] = 0.0;
+    }
     L.cost = 0.0;
     // unrolled over the <= 2 observations of a slot: a runtime-indexed uvq[o] was lowered to a
     // scratch-memory array (a store + reload on the linearisation's critical path)
@@ -467,10 +475,11 @@ __device__ __forceinline__ void slot_linearize(const Geometry& G, const Pose& P,
         if (o >= nobs) break;
         double r[2], J[2][9];
         const double uv[2] = {uvq[o].x, uvq[o].y};
-        linearize(p, P, G.TCB[(cams >> o) & 1].m, uv, r, J, true);
+        linearize(p, P, G.TCB[(cams >> o) & 1].m, uv, r, J, !COST_ONLY);
         double sq = r[0] * r[0] + r[1] * r[1], rho, wt;
         huber(sq, G.huber_delta, &rho, &wt);
         L.cost += 0.5 * rho;
+        if constexpr (COST_ONLY) continue;
         const double wr0 = wt * r[0], wr1 = wt * r[1];
         int k = 0;
 #pragma unroll
@@ -3229,11 +3238,43 @@ __global__ __launch_bounds__(64 * kX2Waves) void ba_camera_solve_x2(Geometry G, 
 // ---------------------------------------------------------------------------------------
 // The wave partials (trial cost, |dp|^2, g_p.dp, |p|^2) go out as plain stores: the decision
 // is taken by the next iteration's K4c blocks (or K7 at the end of a chunk), after the boundary.
-template <bool FUSED>
+//
+// LAST: the form of a chunk's final iteration when the state export is on (single rank).  The
+// chunk's first guess is the previous solve's iteration count, so this iteration is the one
+// expected to converge -- and a decision that ends the solve on a tolerance or the trust region
+// leaves the candidate unapplied: of this K6 only the four trial scalars are then used, and the
+// state to export is the CURRENT buffer, final since the preceding K4c decided.  So this form
+//  (a) copies [pose[cur] | pw[cur]] into hout (pinned host memory, K7's layout) right after the
+//      entry loads, 16 B per store over the grid's threads (both buffers' values loaded with the
+//      entry loads; by index, so landmarks without observations are covered), whatever done /
+//      solve_ok say, and records in tick[2], tick[3] what hout now holds: the solve's stamp
+//      tick[1] and cur + 1.  The stores are posted while the body runs and every wave waits for
+//      their acknowledgement before it ends (export_done), so K7, next in stream order, finds
+//      them complete and skips its own copy when it decides for that buffer (lm_decide_body);
+//  (b) evaluates the trial's cost alone: the same residual and Huber arithmetic
+//      (slot_linearize<COST_ONLY>), no Jacobian blocks and no records.  Should the decision
+//      accept the trial and the solve go on, the host runs this iteration's full K6 again before
+//      the next chunk (enqueue_chunk): same inputs, same trial, plus the records.
+#ifndef RSVIO_EXPORT_FENCE  // build-time A/B: 1 = a full system-scope release fence at the end of
+#define RSVIO_EXPORT_FENCE 0  // every exporting wave (an L2 write-back per wave)
+#endif
+// The end of a wave that wrote into the export buffer: its stores have been acknowledged.  The
+// buffer is fine-grained (uncached) host memory, so an acknowledged store has left the L2 -- and
+// K7's slot stamps, system-scope releases by blocks on every XCD, each write its L2 back first.
+// (A full release fence here made every wave write the L2 back while the others still store
+// their trial points: K6 7.5 us instead of 5.4.)
+__device__ __forceinline__ void export_done() {
+#if RSVIO_EXPORT_FENCE
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+#else
+    __builtin_amdgcn_s_waitcnt(kWaitStores);
+#endif
+}
+template <bool FUSED, bool LAST = false>
 __device__ void k6_body(const Geometry& G, const Prob& Pr, const Work& Wk, int w, int lane, double (*sh)[64],
                         double (*shp)[64], double (*shs)[64], const P2P* PP = nullptr,
                         unsigned long long gen = 0, unsigned long long* k6tag = nullptr,
-                        unsigned long long* k6part = nullptr) {
+                        unsigned long long* k6part = nullptr, double* hout = nullptr) {
     // sh: W_s^T dc_f per slot, then the linearisation scratch; shp: trial point at the
     // landmark's first lane; shs: per-slot trial cost; per-landmark |dp|^2, g_p.dp, |p|^2
     const int s = 64 * w + lane;
@@ -3270,6 +3311,19 @@ __device__ void k6_body(const Geometry& G, const Prob& Pr, const Work& Wk, int w
     }
 #pragma unroll
     for (int i = 0; i < 6; ++i) d6[i] = Wk.dc[6 * fc + i];
+    // LAST: this thread's two values of the export, of both state buffers, with the loads above
+    const int xnp = 7 * G.n_kf, xn = xnp + 3 * G.n_lm;
+    const int xi = (int)min(2ll * s, (long long)xn);  // (>= xn: nothing to copy)
+    double xv[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+    unsigned long long xstamp = 0;
+    if constexpr (LAST) {
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int e = 0; e < 2; ++e)
+                if (xi + e < xn) xv[b][e] = xi + e < xnp ? Wk.pose[b][xi + e] : Wk.pw[b][xi + e - xnp];
+        xstamp = Wk.tick[1];
+    }
     const int done = st->done, solve_ok = st->solve_ok, cur = st->cur;
     const double lambda = st->lambda;
     // keep the compiler from sinking the speculative loads under the branch below
@@ -3283,6 +3337,35 @@ __device__ void k6_body(const Geometry& G, const Prob& Pr, const Work& Wk, int w
         for (int i = 0; i < 3; ++i) __asm__ volatile("" ::"v"(pcb[b][i]));
 #pragma unroll
         for (int i = 0; i < 7; ++i) __asm__ volatile("" ::"v"(p7b[b][i]));
+    }
+    if constexpr (LAST) {
+#pragma unroll
+        for (int e = 0; e < 2; ++e) __asm__ volatile("" ::"v"(xv[0][e]), "v"(xv[1][e]));
+        if (xi < xn) {
+            const double a = cur ? xv[1][0] : xv[0][0];
+            if (xi + 1 < xn)
+                *reinterpret_cast<double2*>(hout + xi) = make_double2(a, cur ? xv[1][1] : xv[0][1]);
+            else
+                hout[xi] = a;
+        }
+        // a state longer than two values per thread of the grid: the rest, strided the same way
+        const double* xpose = Wk.pose[cur];
+        const double* xpw = Wk.pw[cur];
+        for (long long i = xi + 128ll * G.n_wave; i < xn; i += 128ll * G.n_wave) {
+            const double a = i < xnp ? xpose[i] : xpw[i - xnp];
+            if (i + 1 < xn)
+                *reinterpret_cast<double2*>(hout + i) = make_double2(a, i + 1 < xnp ? xpose[i + 1] : xpw[i + 1 - xnp]);
+            else
+                hout[i] = a;
+        }
+        if (s == 0) {  // what hout holds once this kernel has ended
+            Wk.tick[2] = xstamp;
+            Wk.tick[3] = (unsigned long long)(cur + 1);
+        }
+        if (done || !solve_ok) {
+            export_done();  // (as at the body's end)
+            return;
+        }
     }
     if (done || !solve_ok) return;  // no step: the decision (lambda up) is all there is
     STAMP(20);
@@ -3347,16 +3430,18 @@ __device__ void k6_body(const Geometry& G, const Prob& Pr, const Work& Wk, int w
     if (act) {
         const Pose P = pose_from7(p7);
         const double q[3] = {shp[0][first], shp[1][first], shp[2][first]};
-        slot_linearize(G, P, q, h1.y, h1.z, uvq, fr, L);
+        slot_linearize<LAST>(G, P, q, h1.y, h1.z, uvq, fr, L);
     } else {
         const Pose P{};
         const double q[3] = {0.0, 0.0, 1.0};
-        slot_linearize(G, P, q, 0, 0, uvq, false, L);
+        slot_linearize<LAST>(G, P, q, 0, 0, uvq, false, L);
     }
     shs[0][lane] = L.cost;
-    if constexpr (FUSED) wave_sync(); else __syncthreads();  // sh is reused below
-    STAMP(24);
-    store_linearization<FUSED>(Wk, 1 - cur, s, lane, act, fr, first, nk, l, L, sh);
+    if constexpr (!LAST) {
+        if constexpr (FUSED) wave_sync(); else __syncthreads();  // sh is reused below
+        STAMP(24);
+        store_linearization<FUSED>(Wk, 1 - cur, s, lane, act, fr, first, nk, l, L, sh);
+    }
     STAMP(25);
     {  // wave partials: fixed-pairing butterflies over the lanes
         double v[kPartD];
@@ -3393,6 +3478,10 @@ __device__ void k6_body(const Geometry& G, const Prob& Pr, const Work& Wk, int w
                                __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
+    // the export's writer-side fence: a system-scope release by every wave after its own posted
+    // writes, here at the wave's end where they have long been acknowledged -- K7's slot stamps
+    // and ticket (system-scope releases, after the kernel boundary) are ordered behind them
+    if constexpr (LAST) export_done();
     STAMP(21);
     RTSTAMP(8);
 }
@@ -3404,6 +3493,15 @@ __global__ __launch_bounds__(64) void ba_backsub_relinearize(Geometry G, Prob Pr
     RTSTAMP(6);
     k6_body<false>(G, Pr, Wk, blockIdx.x, threadIdx.x, sh, shp, shs);
     RTSTAMP(9);
+}
+
+// K6 of a chunk's final iteration with the state export on (k6_body's LAST form): the current
+// state into hout, then the trial's points and cost without its linearisation
+__global__ __launch_bounds__(64) void ba_backsub_trial_export(Geometry G, Prob Pr, Work Wk, double* hout) {
+    __shared__ double sh[10][64];
+    __shared__ double shp[3][64];
+    __shared__ double shs[4][64];
+    k6_body<false, true>(G, Pr, Wk, blockIdx.x, threadIdx.x, sh, shp, shs, nullptr, 0, nullptr, nullptr, hout);
 }
 
 // K6 of the P2P-sharded iteration with the trial-scalar exchange folded in (RSVIO_P2P_FOLD=2):
@@ -3696,7 +3794,9 @@ __global__ __launch_bounds__(64) void ba_reduce_trial(Geometry G, Prob Pr, Work 
 // state -- poses then points of the current buffers -- into it, and each publishes the solve's
 // start stamp in its own slot htick[4 + block] (release): rsvio_ba_get_state waits for the slots
 // and copies from host memory.  A slice per CU keeps each CU's PCIe writes within one round of
-// outstanding requests (one block writing all 48.6 KB took ~10 us).
+// outstanding requests (one block writing all 48.6 KB took ~10 us).  The copy is skipped when
+// the chunk's last K6 has exported that very buffer of this solve (k6_body's LAST form; its tag
+// in tick[2], tick[3]): a solve that ends without applying its last candidate, the usual end.
 constexpr int kK7Threads = 256;
 #ifndef RSVIO_K7_BLOCKS  // build-time A/B: 48 blocks measured no faster and less stable
 #define RSVIO_K7_BLOCKS 16  // (profiles/r03w_k7_blocks_ab.txt)
@@ -3708,6 +3808,15 @@ __device__ __forceinline__ void lm_decide_body(const Geometry& G, const Prob& Pr
                                                const unsigned long long* xgen = nullptr, int* err = nullptr) {
     STAMP(8);
     __shared__ LmState sd;
+    // what the chunk's last K6 left in hout (k6_body's LAST form; zero before the first one),
+    // loaded with the decision's inputs
+    unsigned long long xstamp = 0, xcur = 0, stamp = 0;
+    if (hout) {
+        stamp = Wk.tick[1];
+        xstamp = Wk.tick[2];
+        xcur = Wk.tick[3];
+        __asm__ volatile("" ::"v"(stamp), "v"(xstamp), "v"(xcur));
+    }
     if (threadIdx.x < 64) {  // the decision by wave 0 of every block
         const LmState d = lm_decide(G, Pr, Wk, Wk.st_prev, pre_reduced, la, PP, xgen, err);
         if (threadIdx.x == 0) {
@@ -3723,25 +3832,32 @@ __device__ __forceinline__ void lm_decide_body(const Geometry& G, const Prob& Pr
     __syncthreads();
     const LmState s = sd;
     if (hout && s.done) {
-        const double* pose = Wk.pose[s.cur];
-        const double* pw = Wk.pw[s.cur];
-        const int np = 7 * G.n_kf, n = np + 3 * G.n_lm;
-        // even slices, written 16 B per store (half the PCIe write requests of 8-B stores)
-        const int per = (((n + (int)gridDim.x - 1) / (int)gridDim.x) + 1) & ~1;
-        const int i0 = (int)blockIdx.x * per, i1 = min(n, i0 + per);
-        for (int i = i0 + 2 * (int)threadIdx.x; i < i1; i += 2 * kK7Threads) {
-            const double a = i < np ? pose[i] : pw[i - np];
-            if (i + 1 < i1) {
-                const double b = i + 1 < np ? pose[i + 1] : pw[i + 1 - np];
-                *reinterpret_cast<double2*>(hout + i) = make_double2(a, b);
-            } else {
-                hout[i] = a;
+        // The chunk's last K6 (the kernel before this one) may have exported this very buffer of
+        // this solve already -- the usual end, a candidate that is not applied: then only the
+        // slot stamps are left to publish.  Otherwise (the last step applied, so cur flipped; no
+        // such K6 in this chunk: sharded, or no K6 wave) the copy is made here.
+        const bool exported = xstamp == stamp && xcur == (unsigned long long)(s.cur + 1);
+        if (!exported) {
+            const double* pose = Wk.pose[s.cur];
+            const double* pw = Wk.pw[s.cur];
+            const int np = 7 * G.n_kf, n = np + 3 * G.n_lm;
+            // even slices, written 16 B per store (half the PCIe write requests of 8-B stores)
+            const int per = (((n + (int)gridDim.x - 1) / (int)gridDim.x) + 1) & ~1;
+            const int i0 = (int)blockIdx.x * per, i1 = min(n, i0 + per);
+            for (int i = i0 + 2 * (int)threadIdx.x; i < i1; i += 2 * kK7Threads) {
+                const double a = i < np ? pose[i] : pw[i - np];
+                if (i + 1 < i1) {
+                    const double b = i + 1 < np ? pose[i + 1] : pw[i + 1 - np];
+                    *reinterpret_cast<double2*>(hout + i) = make_double2(a, b);
+                } else {
+                    hout[i] = a;
+                }
             }
+            __threadfence_system();
+            __syncthreads();
         }
-        __threadfence_system();
-        __syncthreads();
         if (threadIdx.x == 0)
-            __hip_atomic_store(htick + 4 + blockIdx.x, Wk.tick[1], __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(htick + 4 + blockIdx.x, stamp, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         const unsigned long long t = Wk.tick[0] + 1;
@@ -3856,6 +3972,21 @@ __global__ __launch_bounds__(64) void bab_backsub_relinearize(const WinDesc* __r
     __shared__ double shp[3][64];
     __shared__ double shs[4][64];
     k6_body<false>(d.G, Pr, Wk, blockIdx.x, threadIdx.x, sh, shp, shs);
+}
+
+// ba_backsub_trial_export of the descriptor-mode graph (single window: D[0])
+__global__ __launch_bounds__(64) void bab_backsub_trial_export(const WinDesc* __restrict__ D, int wi, double* hout) {
+    const WinDesc& d = D[blockIdx.y];
+    const int skip = d.skip, bound = d.G.n_wave;
+    const Prob Pr = d.Pr;
+    const Work& Wk = d.W[wi];
+    desc_touch(Pr.slot_hdr, Pr.slot_uv, Wk.st, Wk.raws[0], Wk.raws[1], Wk.rawl[0], Wk.rawl[1], Wk.pw[0], Wk.pw[1],
+               Wk.pose[0], Wk.pose[1], Wk.dc, Wk.tick);
+    if (skip | ((int)blockIdx.x >= bound)) return;
+    __shared__ double sh[10][64];
+    __shared__ double shp[3][64];
+    __shared__ double shs[4][64];
+    k6_body<false, true>(d.G, Pr, Wk, blockIdx.x, threadIdx.x, sh, shp, shs, nullptr, 0, nullptr, nullptr, hout);
 }
 
 // Single-window front end of K7 (the handle's graph in descriptor mode, BundleAdjuster::start_graph):
@@ -4218,11 +4349,11 @@ struct BundleAdjuster {
             try {
                 if (dm) {
                     enqueue_start_d(cfg.lambda_init, wcap);
-                    for (int i = 0; i < k; ++i) enqueue_iteration_d(cfg, i, wcap);
+                    for (int i = 0; i < k; ++i) enqueue_iteration_d(cfg, i, wcap, i == k - 1);
                     enqueue_decide_d(cfg, k);
                 } else {
                     enqueue_start(cfg.lambda_init);
-                    for (int i = 0; i < k; ++i) enqueue_iteration(cfg, i);
+                    for (int i = 0; i < k; ++i) enqueue_iteration(cfg, i, i == k - 1);
                     enqueue_decide(cfg, k);
                 }
             } catch (...) {
@@ -4309,6 +4440,17 @@ struct BundleAdjuster {
     bool state_fresh = false;  // set_problem without a run since: get_state resets the buffers first
     // host scratch of set_problem, kept across problems (no per-problem allocations)
     std::vector<int> hs_free, hs_pb_fa, hs_pb_fb;
+    // where and for which free-keyframe pattern the staging image holds pb_fa, pb_fb and dmap
+    struct TablesKey {
+        const uint8_t* base = nullptr;
+        size_t pb_fa = 0, pb_fb = 0, dmap = 0;
+        int n_kf = -1;
+        unsigned fixed = 0;
+        bool operator==(const TablesKey& o) const {
+            return base == o.base && pb_fa == o.pb_fa && pb_fb == o.pb_fb && dmap == o.dmap && n_kf == o.n_kf &&
+                   fixed == o.fixed;
+        }
+    } tables_key;
     DevBuf<double> d_raws, d_rawl, d_partA, d_partD, d_cpart, d_sys, d_dc, d_trial4;
     DevBuf<int> d_singular;
     size_t n_pad = 0;
@@ -4358,8 +4500,8 @@ struct BundleAdjuster {
         // (coarse-grained host memory, the stores gathered in L2 and written back whole by K7's
         // system-scope release, measured the same: profiles/r04k_ab_multi.txt)
         h_out.alloc((size_t)7 * P.max_keyframes + (size_t)3 * P.max_landmarks, hipHostMallocCoherent);
-        d_tick.alloc(2);
-        RSVIO_HIP(hipMemset(d_tick.p, 0, 2 * sizeof(unsigned long long)));
+        d_tick.alloc(4);  // ..., [2] [3] what the last K6 of a chunk exported into h_out (k6_body)
+        RSVIO_HIP(hipMemset(d_tick.p, 0, 4 * sizeof(unsigned long long)));
         RSVIO_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_tick), (4 + kK7Blocks) * sizeof(unsigned long long),
                                 hipHostMallocCoherent));
         std::memset(h_tick, 0, (4 + kK7Blocks) * sizeof(unsigned long long));
@@ -4524,6 +4666,9 @@ struct BundleAdjuster {
             drop_slot(gv);
         solves_of_problem = 0;
         state_export = false;
+        // (a call that fails half way may have written another layout over the tables' place)
+        TablesKey tables_prev = tables_key;
+        tables_key = TablesKey{};
         if (n_kf < 1 || n_kf > P.max_keyframes || n_lm < 0 || n_lm > P.max_landmarks || n_obs < 0 ||
             n_obs > P.max_observations)
             throw std::invalid_argument("problem exceeds the handle's capacities");
@@ -4570,6 +4715,7 @@ struct BundleAdjuster {
         if (up_pending) settle();  // the previous upload may still read the staging image
         if (h_arena.n < L.upload) {
             h_arena.alloc(L.upload + L.upload / 4, hipHostMallocCoherent);
+            tables_prev = TablesKey{};
             void* dp = nullptr;
             RSVIO_HIP(hipHostGetDevicePointer(&dp, h_arena.p, 0));
             h_arena_dev = dp;
@@ -4700,13 +4846,24 @@ struct BundleAdjuster {
         std::memcpy(hb + L.pose_init, pose7, sizeof(double) * 7 * (size_t)n_kf);
         if (n_lm) std::memcpy(hb + L.pw_init, pW, sizeof(double) * 3 * (size_t)n_lm);
         std::memcpy(hb + L.free_idx, free_idx.data(), sizeof(int) * (size_t)n_kf);
-        std::memcpy(hb + L.pb_fa, pb_fa.data(), sizeof(int) * (size_t)n_pb);
-        std::memcpy(hb + L.pb_fb, pb_fb.data(), sizeof(int) * (size_t)n_pb);
-        if (n_free <= 10)
-            mf_dense_map(n_free, n_pb, pb_fa.data(), pb_fb.data(), reinterpret_cast<int*>(hb + L.dmap));
-        else  // the 6x6-block solver's padded template (13 / 16 / 20 free keyframes), leading dimension 129
-            mf_dense_map(n_free, n_pb, pb_fa.data(), pb_fb.data(), reinterpret_cast<int*>(hb + L.dmap),
-                         6 * bk_template_nf(n_free), kBkLd);
+        // pb_fa, pb_fb and the dense map depend on the free-keyframe pattern alone: the staging
+        // image still holds them when the previous problem had the same pattern and put them at
+        // the same place (consecutive windows of a sliding window do)
+        TablesKey tk;
+        tk.base = hb;
+        tk.pb_fa = L.pb_fa; tk.pb_fb = L.pb_fb; tk.dmap = L.dmap;
+        tk.n_kf = n_kf;
+        for (int k = 0; k < n_kf; ++k) tk.fixed |= kf_fixed[k] ? 1u << k : 0u;
+        if (!(tk == tables_prev)) {
+            std::memcpy(hb + L.pb_fa, pb_fa.data(), sizeof(int) * (size_t)n_pb);
+            std::memcpy(hb + L.pb_fb, pb_fb.data(), sizeof(int) * (size_t)n_pb);
+            if (n_free <= 10)
+                mf_dense_map(n_free, n_pb, pb_fa.data(), pb_fb.data(), reinterpret_cast<int*>(hb + L.dmap));
+            else  // the 6x6-block solver's padded template (13 / 16 / 20 free keyframes), leading dimension 129
+                mf_dense_map(n_free, n_pb, pb_fa.data(), pb_fb.data(), reinterpret_cast<int*>(hb + L.dmap),
+                             6 * bk_template_nf(n_free), kBkLd);
+        }
+        tables_key = tk;
         G.n_kf = n_kf; G.n_free = n_free; G.n_lm = n_lm; G.n_obs = n_obs; G.n_slot = (int)n_pad;
         G.n_pb = n_pb; G.n_wave = n_wave; G.n_chunk = n_chunk; G.pair_stride = stride;
         for (int k = 0, run = -1; k < kMaxFree; ++k) {
@@ -4895,7 +5052,10 @@ struct BundleAdjuster {
     // LM iteration `it`: K4c (decision of it - 1 + Schur partials), [K4d + all-reduce], K5, K6,
     // [K6r + all-reduce of the trial scalars].  Its own decision is taken by iteration it + 1's
     // K4c or by enqueue_decide at the end of the chunk.
-    void enqueue_iteration(const rsvio_lm_cfg& cfg, int it) {
+    // last: the final iteration of its chunk -- with the export on (single rank) its K6 is the
+    // LAST form: the current state into h_out, the trial's cost without its linearisation
+    bool lean_last() const { return export_on && !sharded() && G.n_wave > 0; }
+    void enqueue_iteration(const rsvio_lm_cfg& cfg, int it, bool last = false) {
         const Prob pr = prob();
         const Work wk = work(it);
         if (p2p_fold()) {  // sharded over P2P: K4c, K5 with X1 folded in, K6[, X2]
@@ -4945,7 +5105,10 @@ struct BundleAdjuster {
             RSVIO_HIP(hipGetLastError());
             return;
         }
-        if (G.n_wave) hipLaunchKernelGGL(ba_backsub_relinearize, dim3(G.n_wave), dim3(64), 0, stream, G, pr, wk);
+        if (last && lean_last())
+            hipLaunchKernelGGL(ba_backsub_trial_export, dim3(G.n_wave), dim3(64), 0, stream, G, pr, wk, h_out.p);
+        else if (G.n_wave)
+            hipLaunchKernelGGL(ba_backsub_relinearize, dim3(G.n_wave), dim3(64), 0, stream, G, pr, wk);
         RSVIO_HIP(hipGetLastError());
         if (coll == 2) {  // P2P: trial scalars + exchange in one launch (X2)
             hipLaunchKernelGGL(ba_p2p_trial, dim3(1), dim3(256), 0, stream, G, pr, wk, p2p, d_xgen.p, d_p2p_err.p);
@@ -4978,7 +5141,7 @@ struct BundleAdjuster {
         hipLaunchKernelGGL(bab_linearize, dim3(wcap, 1), dim3(64), 0, stream, dptr(), lambda0);
         RSVIO_HIP(hipGetLastError());
     }
-    void enqueue_iteration_d(const rsvio_lm_cfg& cfg, int it, int wcap) {
+    void enqueue_iteration_d(const rsvio_lm_cfg& cfg, int it, int wcap, bool last = false) {
         const int wi = it & 1;  // work(it) depends on the parity of it only
         hipLaunchKernelGGL(bab_schur_chunks, dim3(G.n_chunk, 1), dim3(kSchurThreads), 0, stream, dptr(), wi, lm_args(cfg));
         RSVIO_HIP(hipGetLastError());
@@ -4991,7 +5154,10 @@ struct BundleAdjuster {
             default: throw std::logic_error("descriptor mode: more than 10 free keyframes");
         }
         RSVIO_HIP(hipGetLastError());
-        hipLaunchKernelGGL(bab_backsub_relinearize, dim3(wcap, 1), dim3(64), 0, stream, dptr(), wi);
+        if (last && lean_last())
+            hipLaunchKernelGGL(bab_backsub_trial_export, dim3(wcap, 1), dim3(64), 0, stream, dptr(), wi, h_out.p);
+        else
+            hipLaunchKernelGGL(bab_backsub_relinearize, dim3(wcap, 1), dim3(64), 0, stream, dptr(), wi);
         RSVIO_HIP(hipGetLastError());
     }
     void enqueue_decide_d(const rsvio_lm_cfg& cfg, int it) {
@@ -5011,11 +5177,22 @@ struct BundleAdjuster {
         bool by_tick = false;  // the wait mode fixed at start(): finish() never switches it mid-solve
         rsvio_lm_cfg cfg{};
         int enq = 0, max_it = 0;
+        bool lean = false;  // the last K6 enqueued was the LAST form: no linearisation of its trial
     } pend;
 
     void enqueue_chunk(int k) {
         settled = false;
-        for (int i = 0; i < k; ++i) enqueue_iteration(pend.cfg, pend.enq + i);
+        if (pend.lean) {
+            // the guess was short: the solve goes on, and if the decision accepted the last trial
+            // the next K4c reads its records -- iteration enq - 1's full K6 again.  Its inputs (dc,
+            // the state copy it reads, the records and points of cur, the trial poses) are untouched
+            // since, so it reproduces the same trial and adds the records.
+            hipLaunchKernelGGL(ba_backsub_relinearize, dim3(G.n_wave), dim3(64), 0, stream, G, prob(),
+                               work(pend.enq - 1));
+            RSVIO_HIP(hipGetLastError());
+        }
+        for (int i = 0; i < k; ++i) enqueue_iteration(pend.cfg, pend.enq + i, i == k - 1);
+        pend.lean = lean_last();
         pend.enq += k;
         enqueue_decide(pend.cfg, pend.enq);  // K7 also writes the state into h_state
         ++n_tick;
@@ -5069,6 +5246,7 @@ struct BundleAdjuster {
         if (start_graph(cfg, k)) {
             ++n_tick;
             pend.enq += k;
+            pend.lean = lean_last();
             if (!pend.by_tick) RSVIO_HIP(hipEventRecord(ev1, stream));
         } else {
             enqueue_start(cfg.lambda_init);
