@@ -362,6 +362,64 @@ int rsvio_ba_wait(rsvio_ba* ba, rsvio_ba_result* res);
  * a stream synchronisation; otherwise (or after rsvio_ba_build_system, a skipped solve, a batch
  * run) it is copied from the device buffers. */
 int rsvio_ba_get_state(rsvio_ba* ba, double* pose7, double* p_W);
+/* Landmark triangulation and the depth / reprojection gate, on the device.  The reference creates a
+ * landmark that is not in the map at depth 2.0 along its first observation's ray and leaves two
+ * TODOs (sliding_window.rs:257 "Triangulate instead of assigning depth", :472 "check if points are
+ * estimated at obviously wrong locations"); its configs' `depth: {min_depth: 0.1, max_depth: 100.0}`
+ * section is read by nothing.  Per observation o (keyframe k, camera c, normalised (u, v)):
+ * [R | t] = T_C_B[c] T_B_W(k), centre c_o = -R^T t, unit ray d_o = R^T (u, v, 1)^T / |.|,
+ * M_o = I - d_o d_o^T; per landmark p = (sum M_o)^-1 sum M_o c_o over the observations used:
+ *   RSVIO_TRI_ALL_VIEWS     every observation of the landmark
+ *   RSVIO_TRI_FIRST_STEREO  the two observations of its first keyframe (ascending) that holds both
+ *                           cameras: depends on the extrinsics and ONE pose only, so it is safe while
+ *                           the poses are poor (the bootstrap, every keyframe at identity)
+ * The gate then takes, over the same observations, the depths (R p + t)_z and the squared normalised
+ * reprojection errors.  Flags per landmark (rsvio_landmark_info.flags):
+ *   OK            the point was accepted
+ *   TOO_FEW       fewer than 2 observations used (no stereo keyframe in mode 1); terminal
+ *   DEGENERATE    !(det A > 1e-12 n^3) or not finite, n = observations used (two rays: det A =
+ *                 2 sin^2 of their angle, i.e. parallax below ~2 microradians); terminal
+ *   DEPTH         some depth below min_depth or above max_depth       } both evaluated whenever a
+ *   ERROR         max_sq_error > 0 and the largest squared error > it } point exists; may combine
+ *   NOT_SELECTED  the mask byte is 0 (n_obs and the figures are 0)
+ * n_obs: the observations used; min_depth, max_depth, max_sq_error: over them (0 without a point).
+ * Every sum runs in a fixed order: two calls give identical bits. */
+enum { RSVIO_TRI_ALL_VIEWS = 0, RSVIO_TRI_FIRST_STEREO = 1 };
+enum {
+    RSVIO_LM_OK = 1,
+    RSVIO_LM_TOO_FEW = 2,
+    RSVIO_LM_DEGENERATE = 4,
+    RSVIO_LM_DEPTH = 8,
+    RSVIO_LM_ERROR = 16,
+    RSVIO_LM_NOT_SELECTED = 32
+};
+typedef struct {
+    int32_t mode;                 /* RSVIO_TRI_* */
+    int32_t reserved;
+    double min_depth, max_depth;  /* metres along the optical axis (the reference configs: 0.1, 100.0) */
+    double max_sq_error;          /* squared normalised reprojection error; <= 0: off */
+} rsvio_landmark_gate;            /* 32 bytes */
+typedef struct {
+    int32_t n_obs, flags;
+    double min_depth, max_depth, max_sq_error;
+} rsvio_landmark_info;            /* 32 bytes */
+/* Triangulate the landmarks of the uploaded problem that lm_mask selects (n_lm bytes, NULL = all;
+ * n_lm must be the problem's landmark count) from its INITIAL poses, and write the accepted points
+ * into the device's initial point array, which every later rsvio_ba_run / _run_async / batch run of
+ * this problem starts from (rsvio_ba_solve, the one-shot path, uploads its own).  A rejected or
+ * unselected landmark keeps its uploaded value bit for bit.  Reads poses and observations, never
+ * the points: idempotent.  With all three outputs NULL the call only enqueues on the handle's
+ * stream (set_problem -> triangulate -> run_async has no host wait); otherwise it waits, p_W_out
+ * (n_lm x 3) receives the whole initial point array as the next run will see it, info_out (n_lm)
+ * the report and n_accepted the number of OK landmarks.  Refused while a solve is in flight.  On a
+ * sharded handle it is local (every rank holds all poses and its own landmarks). */
+int rsvio_ba_triangulate(rsvio_ba* ba, const uint8_t* lm_mask, int32_t n_lm, const rsvio_landmark_gate* gate,
+                         double* p_W_out, rsvio_landmark_info* info_out, int32_t* n_accepted);
+/* The gate's report on the state rsvio_ba_get_state would return (the solved state after a solve,
+ * the initial state before one) over ALL observations of every landmark (gate->mode is ignored);
+ * a landmark with no observation reports TOO_FEW.  Writes nothing but info_out (n_lm) and n_ok. */
+int rsvio_ba_check_landmarks(rsvio_ba* ba, int32_t n_lm, const rsvio_landmark_gate* gate,
+                             rsvio_landmark_info* info_out, int32_t* n_ok);
 /* Reduced camera system at `lambda` for the uploaded state (parity tests):
  * S is n x n row-major (n = 6 * free keyframes, ascending keyframe order), b is n. */
 int rsvio_ba_build_system(rsvio_ba* ba, double lambda, double huber_delta, double* S, double* b,

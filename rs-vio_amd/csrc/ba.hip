@@ -4153,6 +4153,9 @@ __global__ __launch_bounds__(256) void ba_p2p_trial(Geometry G, Prob Pr, Work Wk
     p2p_exchange(msg, 4, P, xgen, err, Wk.trial4, gen);
 }
 
+// landmark triangulation and the depth / reprojection gate (ba_landmarks<TRI>)
+#include "ba_landmarks.hpp"
+
 }  // namespace
 
 RSVIO_DBG_READER(rsvio_dbg_ba_stamps)
@@ -4477,6 +4480,17 @@ struct BundleAdjuster {
     DevBuf<unsigned long long> d_k6tag; // fold 3: K6 wave partials, flag-in-word (2 kPartD words per wave);
                                         // fold 4: the plain partials (kPartD words per wave)
     DevBuf<unsigned> d_k6cnt;           // fold 4: K6's ticket counter (back to 0 by the last wave)
+    // landmark triangulation / gate (ba_landmarks): the per-landmark report on the device and its
+    // pinned copy, and the selection mask's pinned staging, which the kernel reads in place
+    // (guarded by ev_sel: an enqueue-only triangulate returns before its kernel has read it) --
+    // sized from max_landmarks at create, so a steady-state call allocates nothing
+    DevBuf<rsvio_landmark_info> d_lm_info;
+    HostBuf<rsvio_landmark_info> h_lm_info;
+    HostBuf<unsigned char> h_lm_sel;
+    const unsigned char* h_lm_sel_dev = nullptr;  // its device address
+    hipEvent_t ev_sel = nullptr;
+    bool sel_pending = false;
+    bool at_initial = false;  // no solve has started since set_problem: the current state is the initial one
 
     void init(const rsvio_ba_params& p) {
         P = p;
@@ -4490,6 +4504,15 @@ struct BundleAdjuster {
         RSVIO_HIP(hipEventCreateWithFlags(&gv.ev_launch, hipEventDisableTiming));
         RSVIO_HIP(hipEventCreateWithFlags(&gd.ev_launch, hipEventDisableTiming));
         RSVIO_HIP(hipEventCreateWithFlags(&ev_desc, hipEventDisableTiming));
+        RSVIO_HIP(hipEventCreateWithFlags(&ev_sel, hipEventDisableTiming));
+        d_lm_info.alloc((size_t)P.max_landmarks);
+        h_lm_info.alloc((size_t)P.max_landmarks);
+        h_lm_sel.alloc((size_t)P.max_landmarks, hipHostMallocCoherent);
+        {
+            void* dp = nullptr;
+            RSVIO_HIP(hipHostGetDevicePointer(&dp, h_lm_sel.p, 0));
+            h_lm_sel_dev = static_cast<const unsigned char*>(dp);
+        }
         const char* fv = std::getenv("RSVIO_P2P_FOLD");  // "0" .. "4" (A/B switch)
         if (fv && fv[0] >= '0' && fv[0] <= '4') fold_lvl = fold_req = fv[0] - '0';
         const char* dv = std::getenv("RSVIO_BA_DESC");  // "0": by-value kernels captured per window
@@ -4546,6 +4569,7 @@ struct BundleAdjuster {
         if (gv.ev_launch) (void)hipEventDestroy(gv.ev_launch);
         if (gd.ev_launch) (void)hipEventDestroy(gd.ev_launch);
         if (ev_desc) (void)hipEventDestroy(ev_desc);
+        if (ev_sel) (void)hipEventDestroy(ev_sel);
         if (stream && own_stream) (void)hipStreamDestroy(stream);
     }
 
@@ -4903,6 +4927,7 @@ struct BundleAdjuster {
         mark();
         *h_state.p = LmState{};  // cur = 0: buffer 0 holds the initial state once it is set
         state_fresh = true;
+        at_initial = true;
         has_problem = true;
         mark();
         if (prof) {
@@ -5230,6 +5255,7 @@ struct BundleAdjuster {
         pend.cfg = cfg;
         pend.by_tick = by_tick();
         state_export = false;
+        at_initial = false;
         // sliding_window.rs:303-319: too few residuals / underconstrained -> skipped (Ok(false))
         if (!sharded() && (G.n_obs < 6 || G.n_obs < G.n_kf + G.n_lm)) {
             pend.skipped = true;
@@ -5573,6 +5599,74 @@ struct BundleAdjuster {
         RSVIO_HIP(hipStreamSynchronize(stream));
     }
 
+    // Triangulation (tri) or the gate's report on the current state (check), enqueued on the
+    // handle's stream.  tri reads the INITIAL poses and the observations -- never the points, so
+    // it is idempotent -- and writes the accepted points of the selected landmarks into the arena's
+    // initial-point array, which every later rsvio_ba_run* / batch run of this problem resets
+    // from; a rejected or unselected landmark keeps its uploaded value.  With no output asked for
+    // it only enqueues (set_problem -> triangulate -> run_async has no host wait); else it waits
+    // and hands back the whole initial point array, the report and the count of accepted points.
+    // check reads what get_state would return and writes nothing but the report.
+    void landmarks(bool tri, const uint8_t* sel, int n_lm, const rsvio_landmark_gate& g, double* pw_out,
+                   rsvio_landmark_info* info_out, int32_t* n_ok) {
+        const char* what = tri ? "triangulate" : "check_landmarks";
+        if (pend.active) throw CallOrderError(std::string(what) + ": a solve is in flight (call rsvio_ba_wait first)");
+        if (!has_problem) throw std::invalid_argument(std::string(what) + ": no problem uploaded");
+        if (n_lm != G.n_lm) throw std::invalid_argument(std::string(what) + ": n_lm differs from the uploaded problem's");
+        if (n_ok) *n_ok = 0;
+        if (!n_lm) return;
+        const unsigned char* d_sel = nullptr;
+        if (tri && sel) {
+            if (sel_pending) RSVIO_HIP(hipEventSynchronize(ev_sel));  // the previous call's kernel has read the staging
+            sel_pending = false;
+            std::memcpy(h_lm_sel.p, sel, (size_t)n_lm);
+            d_sel = h_lm_sel_dev;
+        }
+        const Work wk = work_at(0);
+        const double *pose = wk.pose_init, *pw = wk.pw_init;
+        if (tri) {
+            // (a get_state since set_problem copied the initial state into the state buffers)
+            if (at_initial) state_fresh = true;
+        } else {
+            settle();
+            if (!state_fresh) {
+                const int cur = h_state.p->cur;
+                pose = wk.pose[cur];
+                pw = wk.pw[cur];
+            }
+        }
+        const LmGate gate{tri ? g.mode : (int)RSVIO_TRI_ALL_VIEWS, g.min_depth, g.max_depth, g.max_sq_error};
+        const auto* obs_mask = reinterpret_cast<const unsigned long long*>(d_arena.p + lay.mask);
+        double* pw_init = reinterpret_cast<double*>(d_arena.p + lay.pw_init);
+        const dim3 grid(G.n_wave + (n_lm + 63) / 64), block(64);
+        settled = false;
+        if (tri)
+            hipLaunchKernelGGL(ba_landmarks<true>, grid, block, 0, stream, G, prob(), obs_mask, pose, pw, pw_init, d_sel,
+                               gate, d_lm_info.p);
+        else
+            hipLaunchKernelGGL(ba_landmarks<false>, grid, block, 0, stream, G, prob(), obs_mask, pose, pw, pw_init,
+                               d_sel, gate, d_lm_info.p);
+        RSVIO_HIP(hipGetLastError());
+        if (d_sel) {
+            RSVIO_HIP(hipEventRecord(ev_sel, stream));
+            sel_pending = true;
+        }
+        if (!pw_out && !info_out && !n_ok) return;
+        if (pw_out)
+            RSVIO_HIP(hipMemcpyAsync(pw_out, pw_init, sizeof(double) * 3 * (size_t)n_lm, hipMemcpyDeviceToHost, stream));
+        if (info_out || n_ok)
+            RSVIO_HIP(hipMemcpyAsync(h_lm_info.p, d_lm_info.p, sizeof(rsvio_landmark_info) * (size_t)n_lm,
+                                     hipMemcpyDeviceToHost, stream));
+        settle();
+        sel_pending = false;
+        if (info_out) std::memcpy(info_out, h_lm_info.p, sizeof(rsvio_landmark_info) * (size_t)n_lm);
+        if (n_ok) {
+            int32_t c = 0;
+            for (int l = 0; l < n_lm; ++l) c += (h_lm_info.p[l].flags & RSVIO_LM_OK) ? 1 : 0;
+            *n_ok = c;
+        }
+    }
+
     void build_system(double lambda, double huber_delta, double* S, double* b, double* cost) {
         require_idle("build_system");
         state_export = false;  // K4 below resets the state buffers
@@ -5783,6 +5877,7 @@ struct BundleBatch {
             const LmState& st = h_states.p[i];
             *w.h_state.p = st;
             w.state_fresh = false;
+            w.at_initial = false;
             // the window's stream ran nothing after the event the batch waited on, and the batch
             // stream is synchronised: both are idle
             w.settled = true;
@@ -5884,6 +5979,48 @@ int rsvio_ba_get_state(rsvio_ba* ba, double* pose7, double* p_W) {
     if (!ba || !pose7 || (!p_W && ba->b.G.n_lm)) return RSVIO_ERR_INVALID_ARG;
     return guarded([&] {
         ba->b.get_state(pose7, p_W);
+        return (int)RSVIO_OK;
+    });
+}
+
+static bool gate_ok(const rsvio_landmark_gate* g, const char* what) {
+    if (!g) {
+        rsvio::set_last_error(std::string(what) + ": null gate");
+        return false;
+    }
+    if (g->mode != RSVIO_TRI_ALL_VIEWS && g->mode != RSVIO_TRI_FIRST_STEREO) {
+        rsvio::set_last_error(std::string(what) + ": mode must be RSVIO_TRI_ALL_VIEWS or RSVIO_TRI_FIRST_STEREO");
+        return false;
+    }
+    if (g->min_depth > g->max_depth) {
+        rsvio::set_last_error(std::string(what) + ": min_depth > max_depth");
+        return false;
+    }
+    return true;
+}
+
+int rsvio_ba_triangulate(rsvio_ba* ba, const uint8_t* lm_mask, int32_t n_lm, const rsvio_landmark_gate* gate,
+                         double* p_W_out, rsvio_landmark_info* info_out, int32_t* n_accepted) {
+    if (!ba) {
+        rsvio::set_last_error("rsvio_ba_triangulate: null handle");
+        return RSVIO_ERR_INVALID_ARG;
+    }
+    if (!gate_ok(gate, "rsvio_ba_triangulate")) return RSVIO_ERR_INVALID_ARG;
+    return guarded([&] {
+        ba->b.landmarks(true, lm_mask, n_lm, *gate, p_W_out, info_out, n_accepted);
+        return (int)RSVIO_OK;
+    });
+}
+
+int rsvio_ba_check_landmarks(rsvio_ba* ba, int32_t n_lm, const rsvio_landmark_gate* gate,
+                             rsvio_landmark_info* info_out, int32_t* n_ok) {
+    if (!ba || !info_out) {
+        rsvio::set_last_error("rsvio_ba_check_landmarks: null handle or report");
+        return RSVIO_ERR_INVALID_ARG;
+    }
+    if (!gate_ok(gate, "rsvio_ba_check_landmarks")) return RSVIO_ERR_INVALID_ARG;
+    return guarded([&] {
+        ba->b.landmarks(false, nullptr, n_lm, *gate, nullptr, info_out, n_ok);
         return (int)RSVIO_OK;
     });
 }

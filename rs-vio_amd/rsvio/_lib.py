@@ -76,6 +76,23 @@ class BaParams(C.Structure):
                 ("max_observations", C.c_int32), ("device", C.c_int32)]
 
 
+class LandmarkGate(C.Structure):
+    """rsvio_landmark_gate (32 B): which observations a triangulation uses and the bounds of the gate."""
+    _fields_ = [("mode", C.c_int32), ("reserved", C.c_int32), ("min_depth", C.c_double),
+                ("max_depth", C.c_double), ("max_sq_error", C.c_double)]
+
+
+class LandmarkInfo(C.Structure):
+    """rsvio_landmark_info (32 B): the per-landmark report of rsvio_ba_triangulate / _check_landmarks."""
+    _fields_ = [("n_obs", C.c_int32), ("flags", C.c_int32), ("min_depth", C.c_double),
+                ("max_depth", C.c_double), ("max_sq_error", C.c_double)]
+
+
+# the same record as a numpy dtype (info arrays are filled in place by the library)
+LANDMARK_INFO_DTYPE = [("n_obs", "<i4"), ("flags", "<i4"), ("min_depth", "<f8"), ("max_depth", "<f8"),
+                       ("max_sq_error", "<f8")]
+
+
 class FtConfig(C.Structure):
     """rsvio_ft_config (64 B): FeatureTrackingConfig (feature_tracker/src/feature_tracker.rs:25-38)."""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("nlevels", C.c_int32),
@@ -156,6 +173,8 @@ SIG = {
     "rsvio_upload_async": (C.c_int, [P, P, C.c_size_t, P]),
     "rsvio_ba_wait": (C.c_int, [P, C.POINTER(BaResult)]),
     "rsvio_ba_get_state": (C.c_int, [P, P, P]),
+    "rsvio_ba_triangulate": (C.c_int, [P, P, C.c_int32, C.POINTER(LandmarkGate), P, P, C.POINTER(C.c_int32)]),
+    "rsvio_ba_check_landmarks": (C.c_int, [P, C.c_int32, C.POINTER(LandmarkGate), P, C.POINTER(C.c_int32)]),
     "rsvio_ba_build_system": (C.c_int, [P, C.c_double, C.c_double, P, P, C.POINTER(C.c_double)]),
     "rsvio_rccl_unique_id": (C.c_int, [P, C.c_size_t]),
     "rsvio_ba_attach_comm": (C.c_int, [P, C.c_int32, C.c_int32, P]),

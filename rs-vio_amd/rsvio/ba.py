@@ -6,7 +6,9 @@
   sharding over ranks with an RCCL all-reduce (``attach_comm``).
 * ``SlidingWindow`` -- mirrors ``SlidingWindow`` (sliding_window.rs:21-486): keyframe FIFO,
   problem assembly (stereo-landmark rule, depth-2 initialisation, KF_0 fixed), guards,
-  rollback on failure, map points kept as f32.
+  rollback on failure, map points kept as f32.  Optionally (landmark_init="triangulate", cull)
+  the new landmarks are triangulated on the device and gated landmarks left out of the map: the
+  reference's two TODOs (sliding_window.rs:257, :472).
 """
 from __future__ import annotations
 
@@ -40,6 +42,16 @@ def fallback_cfg(cfg=None):
     c = cfg or lm_cfg()
     return lm_cfg(c.max_iterations, c.cost_tolerance, c.parameter_tolerance, c.huber_delta, c.lambda_init,
                   SOLVER_CHOLESKY)
+
+
+TRI_ALL_VIEWS, TRI_FIRST_STEREO = 0, 1      # RSVIO_TRI_*
+LM_OK, LM_TOO_FEW, LM_DEGENERATE, LM_DEPTH, LM_ERROR, LM_NOT_SELECTED = 1, 2, 4, 8, 16, 32   # RSVIO_LM_* flags
+
+
+def landmark_gate(mode=TRI_FIRST_STEREO, min_depth=0.1, max_depth=100.0, max_sq_error=0.0):
+    """rsvio_landmark_gate; the defaults: the first stereo pair, the reference configs' `depth:`
+    section (min_depth 0.1, max_depth 100.0, read by nothing there), the error bound off."""
+    return _lib.LandmarkGate(mode, 0, min_depth, max_depth, max_sq_error)
 
 
 def _c(a, dt):
@@ -241,6 +253,34 @@ class BundleAdjuster:
         check(_lib.load().rsvio_ba_get_state(self._h, ptr(pose), ptr(pw)))
         return pose, pw
 
+    def triangulate(self, mask=None, gate=None, want=False):
+        """rsvio_ba_triangulate: the landmarks `mask` selects (n_lm bytes, None = all) triangulated
+        from the uploaded initial poses; accepted points replace the initial points the next run /
+        run_async / batch run starts from.  want=False only enqueues (no host wait) and returns
+        None; want=True returns (p_W n_lm x 3 as the next run will see it, info, n_accepted) with
+        info a structured array (_lib.LANDMARK_INFO_DTYPE)."""
+        g = gate or landmark_gate()
+        m = None if mask is None else _c(mask, np.uint8)
+        if m is not None and m.shape != (self.n_lm,):
+            raise ValueError("triangulate(mask=...): one byte per landmark")
+        if not want:
+            check(_lib.load().rsvio_ba_triangulate(self._h, ptr(m), self.n_lm, C.byref(g), None, None, None))
+            return None
+        pw, info = np.empty((self.n_lm, 3)), np.zeros(self.n_lm, _lib.LANDMARK_INFO_DTYPE)
+        n = C.c_int32(0)
+        check(_lib.load().rsvio_ba_triangulate(self._h, ptr(m), self.n_lm, C.byref(g), ptr(pw), ptr(info),
+                                               C.byref(n)))
+        return pw, info, n.value
+
+    def check_landmarks(self, gate=None):
+        """rsvio_ba_check_landmarks: the gate's report on the state state() would return, over all
+        observations -> (info, n_ok)."""
+        g = gate or landmark_gate()
+        info = np.zeros(self.n_lm, _lib.LANDMARK_INFO_DTYPE)
+        n = C.c_int32(0)
+        check(_lib.load().rsvio_ba_check_landmarks(self._h, self.n_lm, C.byref(g), ptr(info), C.byref(n)))
+        return info, n.value
+
     def build_system(self, lam, huber_delta=2.0):
         nfree = int((self._keep[1] == 0).sum())
         S = np.zeros((6 * nfree, 6 * nfree))
@@ -363,7 +403,15 @@ class BundleBatch:
 class SlidingWindow:
     """Keyframe FIFO + BA problem assembly (sliding_window.rs:21-486) over the GPU solver."""
 
-    def __init__(self, max_frames: int, device: int = 0, solver: BundleAdjuster | None = None):
+    def __init__(self, max_frames: int, device: int = 0, solver: BundleAdjuster | None = None,
+                 landmark_init: str = "ray", gate=None, cull: bool = False):
+        """landmark_init: "ray" (the reference's rule: a landmark that is not in the map starts at
+        depth 2.0 along its first observation's ray) or "triangulate" (those landmarks are
+        triangulated on the device from the window's initial poses; one the gate rejects keeps the
+        ray value).  cull: after a successful solve, landmarks the gate rejects on the solved state
+        are left out of the new map.  gate: landmark_gate(...), default landmark_gate()."""
+        if landmark_init not in ("ray", "triangulate"):
+            raise ValueError('landmark_init must be "ray" or "triangulate"')
         self.max_frames = max_frames
         self.keyframes: deque[Frame] = deque()
         # map_points (feature id -> [f32; 3], sliding_window.rs:466-475) as ascending ids + an f32
@@ -374,6 +422,12 @@ class SlidingWindow:
         self.map_version = 0                           # bumped whenever the map is replaced
         self.fallbacks = 0                             # SparseCholesky retries (diagnostic)
         self.solver = solver or BundleAdjuster(max_keyframes=max(max_frames, 2), device=device)
+        self.landmark_init, self.gate, self.cull = landmark_init, gate, bool(cull)
+        need = (("triangulate",) if landmark_init == "triangulate" else ()) + (("check_landmarks",) if cull else ())
+        for name in need + (("set_problem", "run", "state") if need else ()):
+            if not hasattr(self.solver, name):
+                raise ValueError(f"landmark_init / cull need a solver with {name}()")
+        self.last_triangulation = None                 # (selected, accepted) of the last window solved
         self.last_result = None
         self._pending = None                           # landmark ids of a solve in flight (optimize_async)
 
@@ -447,6 +501,20 @@ class SlidingWindow:
         if len(lm) < 6 or len(lm) < num_vars:
             self.last_result = None
             return False
+        if self._split():
+            # the split path: upload, triangulate the landmarks that are not in the map, solve; the
+            # SparseCholesky retry starts from the same (triangulated) initial state on the device
+            self.solver.set_problem(pose7, fixed, p_init, lm, kf, cam, uv, tcb)
+            if self.landmark_init == "triangulate":
+                mask = self._new_mask(ids)
+                _, _, accepted = self.solver.triangulate(mask, self.gate, want=True)
+                self.last_triangulation = (int(mask.sum()), accepted)
+            res = self.solver.run(cfg)
+            if res.status == LINEAR_SOLVE_FAILED:
+                self.fallbacks += 1
+                res = self.solver.run(fallback_cfg(cfg))
+            pose, pw = self.solver.state()
+            return self._apply(*self._culled(ids, pose, pw, res))
         pose, pw, res = self.solver.solve(pose7, fixed, p_init, lm, kf, cam, uv, tcb, cfg)
         if res.status == LINEAR_SOLVE_FAILED:
             # sliding_window.rs:326-353: a singular Schur solve is retried from the same initial
@@ -454,6 +522,26 @@ class SlidingWindow:
             self.fallbacks += 1
             pose, pw, res = self.solver.solve(pose7, fixed, p_init, lm, kf, cam, uv, tcb, fallback_cfg(cfg))
         return self._apply(ids, pose, pw, res)
+
+    def _split(self) -> bool:
+        return self.landmark_init == "triangulate" or self.cull
+
+    def _new_mask(self, ids) -> np.ndarray:
+        """One byte per landmark: 1 where its id is not in the map (the landmarks the reference
+        starts on the depth-2.0 ray, sliding_window.rs:248-262)."""
+        if not len(self.map_ids):
+            return np.ones(len(ids), np.uint8)
+        pos = np.minimum(np.searchsorted(self.map_ids, ids), len(self.map_ids) - 1)
+        return (self.map_ids[pos] != ids).astype(np.uint8)
+
+    def _culled(self, ids, pose, pw, res):
+        """cull: after a successful solve, the landmarks whose report on the solved state lacks OK
+        (the gate's depth / error bounds, sliding_window.rs:472's TODO) stay out of the new map."""
+        if self.cull and res.status > 0 and len(ids):
+            info, _ = self.solver.check_landmarks(self.gate)
+            keep = (info["flags"] & LM_OK) != 0
+            ids, pw = np.asarray(ids)[keep], np.asarray(pw).reshape(-1, 3)[keep]
+        return ids, pose, pw, res
 
     def _apply(self, ids, pose, pw, res) -> bool:
         """process_optimization_result (sliding_window.rs:418-486), by the library's host code
@@ -494,18 +582,28 @@ class SlidingWindow:
             self.last_result = None
             return False
         self.solver.set_problem(pose7, fixed, p_init, lm, kf, cam, uv, tcb)
+        mask = None
+        if self.landmark_init == "triangulate":  # enqueued only: no host wait before run_async
+            mask = self._new_mask(ids)
+            self.solver.triangulate(mask, self.gate, want=False)
         self.solver.run_async(cfg)
-        self._pending = (ids, cfg)
+        self._pending = (ids, cfg, mask)
         return None
 
     def finish(self):
         """Complete a solve started by optimize_async (no-op otherwise); returns its bool."""
         if self._pending is None:
             return None
-        (ids, cfg), self._pending = self._pending, None
+        (ids, cfg, mask), self._pending = self._pending, None
         res = self.solver.wait()
+        if mask is not None:
+            # the count the enqueue-only call could not return: triangulate reads the initial poses
+            # and the observations alone, so the same call now gives the same report (and rewrites
+            # the same initial points)
+            _, _, accepted = self.solver.triangulate(mask, self.gate, want=True)
+            self.last_triangulation = (int(mask.sum()), accepted)
         if res.status == LINEAR_SOLVE_FAILED:  # the SparseCholesky retry (:326-353), same problem
             self.fallbacks += 1
             res = self.solver.run(fallback_cfg(cfg))
         pose, pw = self.solver.state()
-        return self._apply(ids, pose, pw, res)
+        return self._apply(*self._culled(ids, pose, pw, res))

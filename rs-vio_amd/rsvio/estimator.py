@@ -115,10 +115,13 @@ class Estimator:
     def __init__(self, width: int, height: int, cameras, T_B_Cl, T_B_Cr, levels: int = 6, grid_size: int = 50,
                  max_iterations: int = 20, thresh: float = 0.01, window: int = 10,
                  translation_threshold: float = 0.05, rotation_threshold: float = 0.05, device: int = 0,
-                 backend=None, pipelined: bool = False):
+                 backend=None, pipelined: bool = False, landmark_init: str = "ray", gate=None, cull: bool = False):
         self.backend = backend or DeviceBackend(width, height, cameras, levels, grid_size, max_iterations, thresh,
                                                 window, translation_threshold, rotation_threshold, device)
-        self.window = SlidingWindow(window, device, solver=self.backend.solver)
+        # landmark_init / gate / cull: the window's (SlidingWindow): new landmarks triangulated on the
+        # device instead of the depth-2.0 ray, gated landmarks left out of the map
+        self.window = SlidingWindow(window, device, solver=self.backend.solver, landmark_init=landmark_init,
+                                    gate=gate, cull=cull)
         self.T_B_Cl = np.asarray(T_B_Cl, np.float64)
         self.T_B_Cr = np.asarray(T_B_Cr, np.float64)
         self.frame_id = 0
@@ -232,7 +235,9 @@ class NativeEstimator:
     (lib/librsvio_host.so, rs-vio_amd/driver/estimator.cpp): the same steps over the same
     DeviceBackend handles, as the reference's compiled Rust estimator runs them -- no interpreter
     between the device calls.  Frame for frame the same outputs as Estimator(pipelined=True).run
-    (tests/test_estimator_gpu.py); `stats` holds the host wall time per stage."""
+    (tests/test_estimator_gpu.py); `stats` holds the host wall time per stage.  The native loop
+    keeps the reference's depth-2.0 ray rule for new landmarks: device triangulation and culling
+    (SlidingWindow's landmark_init / cull) are options of the Python Estimator only."""
 
     _INT_NONE = -(2 ** 31)
 
