@@ -45,6 +45,7 @@
 
 #include "common.hpp"
 
+#include "ba_envelope.hpp"  // host: the camera system's symbolic envelope
 #include "obs_pass.hpp"  // host: set_problem's observation pass
 #include "se3.hpp"
 #include "wave.hpp"
@@ -61,6 +62,7 @@ RSVIO_DBG_DECL
 RSVIO_RT_DECL
 
 constexpr int kMaxFree = 20;            // camera system up to 120 x 120 in LDS
+static_assert(kMaxFree == rsvio_env::kMaxFree, "ba_envelope.hpp sizes env[] for the same camera system");
 constexpr int kMaxN = 6 * kMaxFree;
 // Raw linearisation per slot, one contiguous 224-B record (AoS).  factors.rs:437-441: the
 // translation columns of the 2x9 Jacobian equal the point columns (J = [Jp | Jp | Jr]), so of a
@@ -4813,29 +4815,15 @@ struct BundleAdjuster {
         int n_wave = 0, fill = 0;
         int gl[kGrp] = {0, 0, 0, 0, 0, 0, 0, 0};
         // the camera system's symbolic envelope (the 6x6-block solver past 10 free keyframes
-        // skips the tiles outside it): a landmark couples every free keyframe between its first
-        // and last one (a superset of its pairs); cand[a] = the last keyframe of the landmarks
-        // starting at a, env[k] = the prefix maximum (the rows of L's column block k that may be
-        // nonzero: LDL^T keeps the envelope)
-        const bool want_env = n_free > 10;
-        unsigned long long freebits = 0;
-        for (int k = 0; k < n_kf; ++k)
-            if (free_idx[k] >= 0) freebits |= 1ull << (2 * k);
-        int cand[kMaxFree];
-        for (int k = 0; k < kMaxFree; ++k) cand[k] = -1;
+        // skips the tiles outside it), gathered from the masks in this loop: ba_envelope.hpp
+        rsvio_env::Envelope envelope(free_idx.data(), n_kf, n_free);
         for (int l = 0; l < n_lm; ++l) {
             const int ns = slot_count(m2[l]);
             if (!ns) {
                 lm_base[l] = -1;
                 continue;
             }
-            if (want_env) {
-                const unsigned long long kb = (m2[l] | (m2[l] >> 1)) & freebits;
-                if (kb) {
-                    const int a = free_idx[__builtin_ctzll(kb) >> 1], b = free_idx[(63 - __builtin_clzll(kb)) >> 1];
-                    cand[a] = std::max(cand[a], b);
-                }
-            }
+            envelope.add(m2[l]);
             if (n_wave == 0 || fill + ns > 64) {
                 if (n_wave) wave_fill[n_wave - 1] = fill;
                 wave_lm[n_wave] = l;
@@ -4890,11 +4878,7 @@ struct BundleAdjuster {
         tables_key = tk;
         G.n_kf = n_kf; G.n_free = n_free; G.n_lm = n_lm; G.n_obs = n_obs; G.n_slot = (int)n_pad;
         G.n_pb = n_pb; G.n_wave = n_wave; G.n_chunk = n_chunk; G.pair_stride = stride;
-        for (int k = 0, run = -1; k < kMaxFree; ++k) {
-            run = std::max(run, cand[k]);
-            G.env[k] = (unsigned char)(k >= n_free ? k : want_env ? std::max(k, run) : n_free - 1);
-        }
-        G.env_on = want_env ? 1 : 0;
+        envelope.finish(G.env, &G.env_on);
         for (int c = 0; c < 2; ++c)
             for (int i = 0; i < 16; ++i) G.TCB[c].m[i] = TCB2[16 * c + i];
         grow_buffers();  // (before the descriptor: it holds their addresses)
@@ -5053,10 +5037,16 @@ struct BundleAdjuster {
             default: {
                 if (k5_variant == 2) {  // the 6x6-block solver with MFMA updates (the default)
                     const dim3 b3(64 * kBkWaves);
+                    // sharded: the all-reduced system couples the keyframes of every rank's
+                    // landmarks, G.env only this rank's (it still bounds this rank's chunks) --
+                    // the factorisation takes the dense envelope.  Decided here, at the launch, so
+                    // that the order of attach and set_problem cannot matter.
+                    Geometry Gk = G;
+                    if (sharded()) rsvio_env::dense_envelope(G.n_free, Gk.env);
                     switch (bk_template_nf(G.n_free)) {
-                        case 13: hipLaunchKernelGGL(ba_camera_solve_blk<13>, g, b3, 0, stream, G, pr, wk, combine); break;
-                        case 16: hipLaunchKernelGGL(ba_camera_solve_blk<16>, g, b3, 0, stream, G, pr, wk, combine); break;
-                        default: hipLaunchKernelGGL(ba_camera_solve_blk<20>, g, b3, 0, stream, G, pr, wk, combine); break;
+                        case 13: hipLaunchKernelGGL(ba_camera_solve_blk<13>, g, b3, 0, stream, Gk, pr, wk, combine); break;
+                        case 16: hipLaunchKernelGGL(ba_camera_solve_blk<16>, g, b3, 0, stream, Gk, pr, wk, combine); break;
+                        default: hipLaunchKernelGGL(ba_camera_solve_blk<20>, g, b3, 0, stream, Gk, pr, wk, combine); break;
                     }
                     break;
                 }

@@ -295,6 +295,134 @@ def ba_problem(n_kf: int = 10, n_lm: int = 2000, kf_per_lm: int = 6, seed: int =
                      true_pose7=true_pose7, true_p_W=p_W)
 
 
+def ba_problem_from_visibility(vis, cam_vis=None, fixed=(0,), seed: int = 7, noise_px: float = 0.5,
+                               init_seed: int = 11, pose_noise=(0.02, math.radians(0.5)),
+                               depth_noise: float = 0.05) -> BAProblem:
+    """A window with explicit visibility: vis (n_lm, n_kf) bool says which keyframes see which
+    landmark, cam_vis (n_lm, n_kf, 2) bool which of the two cameras (None: both); the keyframes in
+    `fixed` are fixed and start at their true pose.  The scene (trajectory, landmark volume), the
+    noise model and the f32-widened observations are ba_problem's; the observations are
+    landmark-major, keyframes ascending, left camera first.  A landmark may have no observation."""
+    vis = np.asarray(vis, bool)
+    n_lm, n_kf = vis.shape
+    cam_vis = np.ones((n_lm, n_kf, 2), bool) if cam_vis is None else np.asarray(cam_vis, bool)
+    see = vis[:, :, None] & cam_vis
+    rng = np.random.default_rng(seed)
+    T_W_B = []
+    for k in range(n_kf):
+        T = np.eye(4)
+        T[:3, :3] = rot_z(0.01 * k)
+        T[:3, 3] = [0.08 * k, 0.01 * math.sin(k), 0.0]
+        T_W_B.append(T)
+    T_C_B = [np.linalg.inv(T_B_CL), np.linalg.inv(T_B_CR)]
+    T_C_W = [[T_C_B[c] @ np.linalg.inv(T_W_B[k]) for c in range(2)] for k in range(n_kf)]
+    p_c0 = np.stack([rng.uniform(-3, 3, n_lm), rng.uniform(-2, 2, n_lm), rng.uniform(2, 8, n_lm)], 1)
+    T_W_C0 = T_W_B[0] @ T_B_CL
+    p_W = (T_W_C0[:3, :3] @ p_c0.T).T + T_W_C0[:3, 3]
+    obs_lm, obs_kf, obs_cam, obs_uv = [], [], [], []
+    sig = noise_px / FX_LEFT
+    for l, k, c in zip(*np.nonzero(see)):  # (row-major: landmark, keyframe, camera)
+        T = T_C_W[k][c]
+        pc = T[:3, :3] @ p_W[l] + T[:3, 3]
+        obs_lm.append(l)
+        obs_kf.append(k)
+        obs_cam.append(c)
+        obs_uv.append(pc[:2] / pc[2] + rng.normal(0.0, sig, 2))
+    true_pose7 = np.stack([pose7_from_T_W_B(T) for T in T_W_B])
+    kf_fixed = np.zeros(n_kf, np.uint8)
+    kf_fixed[list(fixed)] = 1
+    rng2 = np.random.default_rng(init_seed)
+    pose7 = true_pose7.copy()
+    for k in range(n_kf):
+        if kf_fixed[k]:
+            continue
+        T = T_W_B[k].copy()
+        T[:3, :3] = small_rot(rng2, pose_noise[1]) @ T[:3, :3]
+        T[:3, 3] += rng2.normal(0.0, pose_noise[0] / math.sqrt(3.0), 3)
+        pose7[k] = pose7_from_T_W_B(T)
+    scale = 1.0 + rng2.uniform(-depth_noise, depth_noise, n_lm)
+    p_init = (T_W_C0[:3, :3] @ (p_c0 * scale[:, None]).T).T + T_W_C0[:3, 3]
+    return BAProblem(pose7=pose7, kf_fixed=kf_fixed, p_W=np.ascontiguousarray(p_init),
+                     obs_lm=np.asarray(obs_lm, np.int32), obs_kf=np.asarray(obs_kf, np.int32),
+                     obs_cam=np.asarray(obs_cam, np.uint8),
+                     obs_uv=np.asarray(obs_uv, np.float64).reshape(-1, 2).astype(np.float32).astype(np.float64),
+                     T_C_B2=np.stack([T_C_B[0].reshape(16), T_C_B[1].reshape(16)]),
+                     true_pose7=true_pose7, true_p_W=np.ascontiguousarray(p_W))
+
+
+# Named visibility patterns: (n_kf, n_lm, rng) -> (vis, cam_vis or None, fixed keyframes).  They
+# are what ba_problem's landmarks over consecutive keyframes never give the camera system: its
+# symbolic envelope (csrc/ba_envelope.hpp) is a narrow band there.
+def _spans(n_kf, n, span, rng):
+    vis = np.zeros((n, n_kf), bool)
+    for l, s in enumerate(rng.integers(0, n_kf - span + 1, n)):
+        vis[l, s:s + span] = True
+    return vis
+
+
+def vis_two_ended(n_kf, n_lm, rng):
+    """Spans of 4, then 4 landmarks seen only at keyframe 1 and at the last one: the first free
+    column reaches the last block row, and fill-in makes every later column reach it too."""
+    vis = np.concatenate([_spans(n_kf, n_lm - 4, 4, rng), np.zeros((4, n_kf), bool)])
+    vis[-4:, [1, n_kf - 1]] = True
+    return vis, None, (0,)
+
+
+def vis_full_span(n_kf, n_lm, rng):
+    """Every landmark in every keyframe: a dense system, nothing may be skipped."""
+    return np.ones((n_lm, n_kf), bool), None, (0,)
+
+
+def vis_random_gaps(n_kf, n_lm, rng):
+    """Each landmark in a random subset of 3..6 keyframes."""
+    vis = np.zeros((n_lm, n_kf), bool)
+    for l in range(n_lm):
+        vis[l, rng.choice(n_kf, int(rng.integers(3, 7)), replace=False)] = True
+    return vis, None, (0,)
+
+
+def vis_staircase(n_kf, n_lm, rng):
+    """Landmarks in creation order (a sliding window's numbering): landmark l starts at keyframe
+    l (n_kf - 2) // n_lm and spans 2 + start % 5 keyframes (clipped): an envelope strictly inside
+    the dense one whose edges fall at many row offsets, and that differs between contiguous shards."""
+    vis = np.zeros((n_lm, n_kf), bool)
+    for l in range(n_lm):
+        s = l * (n_kf - 2) // n_lm
+        vis[l, s:min(s + 2 + s % 5, n_kf)] = True
+    return vis, None, (0,)
+
+
+def vis_two_fixed_mono(n_kf, n_lm, rng):
+    """Spans of 5 with keyframes 0 and 5 fixed; the left camera misses each landmark's last
+    keyframe and the right camera its first.  The last three landmarks: two seen only from the
+    fixed keyframes, one with no observation at all."""
+    vis = np.concatenate([_spans(n_kf, n_lm - 3, 5, rng), np.zeros((3, n_kf), bool)])
+    cam = np.ones((n_lm, n_kf, 2), bool)
+    for l in range(n_lm - 3):
+        ks = np.nonzero(vis[l])[0]
+        cam[l, ks[-1], 0] = False
+        cam[l, ks[0], 1] = False
+    vis[-3:-1, [0, 5]] = True
+    return vis, cam, (0, 5)
+
+
+VIS_PATTERNS = {"two_ended": vis_two_ended, "full_span": vis_full_span, "random_gaps": vis_random_gaps,
+                "staircase": vis_staircase, "two_fixed_mono": vis_two_fixed_mono}
+
+
+def pattern_visibility(name: str, n_kf: int):
+    """A named pattern at the size the envelope tests use: 30 landmarks per keyframe (10 for
+    full_span), the smallest at which every camera block still has landmarks."""
+    n_lm = (10 if name == "full_span" else 30) * n_kf
+    return VIS_PATTERNS[name](n_kf, n_lm, np.random.default_rng(300 + n_kf))
+
+
+def ba_pattern_problem(name: str, n_kf: int) -> BAProblem:
+    """The window of pattern_visibility(name, n_kf)."""
+    vis, cam, fixed = pattern_visibility(name, n_kf)
+    return ba_problem_from_visibility(vis, cam, fixed, seed=100 + n_kf, init_seed=200 + n_kf)
+
+
 def eucm_project(params, xy: np.ndarray) -> np.ndarray:
     """EUCM projection (Khomutenko et al.; camera-intrinsic-model's EUCM, src/datasets/mod.rs:102-113)
     of the rays (x, y, 1): u = fx x / (alpha d + (1 - alpha) z) + cx, d = sqrt(beta (x^2 + y^2) + z^2).

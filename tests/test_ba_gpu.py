@@ -120,6 +120,10 @@ def test_cheirality_and_skip(gpu, oracle):
 
 
 def test_config5_shape_matches_oracle(gpu, oracle):
+    """Config 5's size (19 free keyframes, 80,000 observations).  Its landmarks span 8 consecutive
+    keyframes, so the camera system is the narrowest band the symbolic envelope can be; the
+    non-banded windows (fill-in, gaps, a dense system, interior fixed keyframes, one-camera
+    keyframes, batched and sharded) are tests/test_ba_envelope_gpu.py's."""
     from rsvio import synthetic as S
     prob = S.ba_problem(n_kf=20, n_lm=5000, kf_per_lm=8, seed=55, init_seed=56)
     assert prob.n_obs == 80000
