@@ -839,6 +839,18 @@ int rsvio_pnp_set_map(rsvio_pnp* h, const uint64_t* ids, const float* p_W, int32
     });
 }
 
+// Diagnostic (host only, not part of the ABI header): the shape of the table the last set_map
+// built -> {buckets, max_probe, has_top, n_map}
+int rsvio_dbg_pnp_map_stats(rsvio_pnp* h, int32_t out[4]) {
+    if (!h || !out) return RSVIO_ERR_INVALID_ARG;
+    const auto& P = h->p;
+    out[0] = (int32_t)(P.htable.size() / rsvio::kBucket);
+    out[1] = P.max_probe;
+    out[2] = P.has_top;
+    out[3] = P.n_map;
+    return RSVIO_OK;
+}
+
 int rsvio_track_motion(rsvio_pnp* h, const uint64_t* ids_l, const float* uv_l, size_t n_l, const uint64_t* ids_r,
                        const float* uv_r, size_t n_r, const double* T_W_B_last_kf, const double* T_C_B2,
                        const rsvio_lm_cfg* cfg, const rsvio_keyframe_rule* rule, rsvio_motion_result* res) {

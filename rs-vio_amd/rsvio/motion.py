@@ -81,6 +81,17 @@ class MotionTracker:
         check(_lib.load().rsvio_pnp_set_map(self._h, ptr(ids), ptr(p_W), len(ids)))
         self.n_map = len(ids)
 
+    def map_stats(self) -> dict:
+        """Diagnostic (rsvio_dbg_pnp_map_stats): the hash table the last set_map built --
+        buckets, max_probe (the longest bucket run an insertion took), has_top (the id 2^64 - 1 is
+        in the map, carried beside the table) and n_map."""
+        fn = _lib.load().rsvio_dbg_pnp_map_stats
+        fn.argtypes = [C.c_void_p, C.c_void_p]
+        fn.restype = C.c_int
+        out = np.zeros(4, np.int32)
+        check(fn(self._h, ptr(out)))
+        return dict(buckets=int(out[0]), max_probe=int(out[1]), has_top=int(out[2]), n_map=int(out[3]))
+
     def track_motion(self, ids_l, uv_l, ids_r, uv_r, T_W_B_last_kf, T_C_B2, cfg=None) -> MotionResult:
         ids_l = np.ascontiguousarray(ids_l, np.uint64).reshape(-1)
         ids_r = np.ascontiguousarray(ids_r, np.uint64).reshape(-1)

@@ -52,7 +52,8 @@ def test_track_motion_matches_oracle(motion, oracle, seed, step, outliers):
 
 
 def test_track_motion_thresholds_and_large_map(motion, oracle):
-    """A map larger than the LDS-staged join (global binary search) and the TUM-VI thresholds."""
+    """A 9,000-point map (a 16,384-bucket hash table, built on the host by set_map and probed by
+    map_lookup) and the TUM-VI thresholds."""
     from rsvio import synthetic as S
     from rsvio.motion import MotionTracker
     m = S.motion_frame(seed=11, n_map=9000, n_feat=800, step=(0.2, math.radians(10)))
