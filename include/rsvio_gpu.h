@@ -420,6 +420,42 @@ int rsvio_ba_triangulate(rsvio_ba* ba, const uint8_t* lm_mask, int32_t n_lm, con
  * a landmark with no observation reports TOO_FEW.  Writes nothing but info_out (n_lm) and n_ok. */
 int rsvio_ba_check_landmarks(rsvio_ba* ba, int32_t n_lm, const rsvio_landmark_gate* gate,
                              rsvio_landmark_info* info_out, int32_t* n_ok);
+/* Pose and landmark covariance from the reduced camera system, on the device.  x is the state
+ * rsvio_ba_get_state would return (the solved state after a solve or a batch run, the initial
+ * state before one).  H = sum_obs w J^T J is the Gauss-Newton Hessian of the BA cost at x with no
+ * damping (lambda = 0): J is BundleAdjustmentFactor::linearize's 2x9 [dp_W | dt | dw]
+ * (factors.rs:350-447, zero on its cheirality branch), w the Huber IRLS weight at huber_delta, the
+ * pose columns those of the free keyframes in ascending order, in the tangent the LM's (+) uses
+ * (se3_plus: [dt; dw] of T_B_W).
+ *   pose covariance      Sigma_cc    = S^-1,  S = U - W V^-1 W^T at lambda = 0,  n = 6 n_free <= 120
+ *   landmark covariance  Sigma_pp(l) = V_l^-1 + sum_{a,b} Y_a^T Sigma_cc[a,b] Y_b,  Y_k = W_k V_l^-1,
+ *                        over the landmark's slots in free keyframes (only fixed ones: V_l^-1)
+ * Units: normalised-image-coordinate^2 per unit measurement variance -- the caller multiplies by
+ * its sigma^2; no sigma is assumed here.
+ * info->status:
+ *   RSVIO_COV_OK                 the outputs are written
+ *   RSVIO_COV_LANDMARK_SINGULAR  n_singular landmarks with observations have a V that fails the
+ *                                solve's det > 0 test (the rule of RSVIO_LM_LINEAR_SOLVE_FAILED)
+ *   RSVIO_COV_CAMERA_SINGULAR    a pivot of S was not positive and finite (e.g. no fixed keyframe)
+ * On a negative status no covariance output is written; the function still returns RSVIO_OK.
+ * cov_cc (n x n row-major, exactly symmetric), cov_pose (n_kf x 36: each keyframe's 6x6 diagonal
+ * block of cov_cc, zeros for a fixed keyframe) may be NULL.  lm_idx selects n_sel landmarks (repeats
+ * allowed; NULL with n_sel == n_lm: every landmark; n_sel 0: none, cov_lm and lm_flags may be NULL);
+ * cov_lm is n_sel x 9, lm_flags n_sel: LM_OK, or LM_NOT_OBSERVED (no observation: zeros).
+ * info->cost is the cost at x, device_ms the call's own kernels by HIP events.  The state, and what
+ * any later run computes, is untouched; every sum runs in a fixed order (two calls: the same bits).
+ * Refused while a solve is in flight and on a sharded handle; an lm_idx entry out of range is
+ * RSVIO_ERR_INVALID_ARG. */
+enum { RSVIO_COV_OK = 1, RSVIO_COV_CAMERA_SINGULAR = -1, RSVIO_COV_LANDMARK_SINGULAR = -2 };
+enum { RSVIO_COV_LM_OK = 1, RSVIO_COV_LM_NOT_OBSERVED = 2 };
+typedef struct { int32_t status, n_free, n_singular, reserved; double cost, device_ms; } rsvio_cov_info;
+int rsvio_ba_covariance(rsvio_ba* ba, double huber_delta,
+                        double* cov_cc,     /* n x n row-major, or NULL */
+                        double* cov_pose,   /* n_kf x 36: each keyframe's 6x6 diagonal block, zeros for a fixed one, or NULL */
+                        const int32_t* lm_idx, int32_t n_sel,  /* NULL + n_sel == n_lm: every landmark; n_sel 0: none */
+                        double* cov_lm,     /* n_sel x 9 */
+                        uint8_t* lm_flags,  /* n_sel */
+                        rsvio_cov_info* info);
 /* Reduced camera system at `lambda` for the uploaded state (parity tests):
  * S is n x n row-major (n = 6 * free keyframes, ascending keyframe order), b is n. */
 int rsvio_ba_build_system(rsvio_ba* ba, double lambda, double huber_delta, double* S, double* b,

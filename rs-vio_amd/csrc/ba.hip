@@ -2206,11 +2206,13 @@ __device__ bool combine_p2p(const Geometry& G, const Prob& Pr, const Work& Wk, d
 // and column J+2 are updated from readlanes of the unscaled column u; columns >= J+3 from values
 // of u read this step and consumed one step later (uq, with the pivot's l as lp) -- by readlane
 // since round 6 (LDS broadcasts before: their wait sat between two pivots' chains).
-template <int H, int J, int PW>
+template <int H, int J, int PW, bool KD = false>
 __device__ __forceinline__ void mf_pivot(double (&a)[kMfPanel], double (&uq)[kMfPanel], double lp, double inv,
-                                         double* Lf, double* Up, int lane, bool& bad) {
+                                         double* Lf, double* Up, int lane, bool& bad, double* Dv = nullptr) {
     constexpr int K = kMfPanel * H + J;
     const double u = a[J];
+    if constexpr (KD)  // 1 / d_K kept (the covariance inverts the factor)
+        if (lane == 0) Dv[K] = inv;
     double inv_next = 1.0;
     double uk1 = 0.0;
     if constexpr (J + 1 < PW) {
@@ -2254,12 +2256,13 @@ __device__ __forceinline__ void mf_pivot(double (&a)[kMfPanel], double (&uq)[kMf
 #pragma unroll
     for (int jj = J + 3; jj < PW; ++jj) uq[jj] = Up[J * kMfLd + kMfPanel * H + jj];  // broadcasts
 #endif
-    if constexpr (J + 1 < PW) mf_pivot<H, J + 1, PW>(a, uq, l, inv_next, Lf, Up, lane, bad);
+    if constexpr (J + 1 < PW) mf_pivot<H, J + 1, PW, KD>(a, uq, l, inv_next, Lf, Up, lane, bad, Dv);
 }
 
 // Panel H (columns 8H .. 8H + PW - 1) factored by wave 0 from M into Lf and its U buffer Uh.
-template <int NF, int H>
-__device__ __forceinline__ void mf_factor(const double* M, double* Lf, double* Uh, int lane, bool& bad) {
+template <int NF, int H, bool KD = false>
+__device__ __forceinline__ void mf_factor(const double* M, double* Lf, double* Uh, int lane, bool& bad,
+                                          double* Dv = nullptr) {
     constexpr int NP = MfDims<NF>::NP;
     constexpr int C0 = kMfPanel * H;
     constexpr int PW = (NP - C0) < kMfPanel ? (NP - C0) : kMfPanel;
@@ -2271,7 +2274,7 @@ __device__ __forceinline__ void mf_factor(const double* M, double* Lf, double* U
     }
     const double piv = rl64(a[0], C0);
     bad |= !(piv > 0.0) || !isfinite(piv);
-    mf_pivot<H, 0, PW>(a, uq, 0.0, rcp_f64(piv), Lf, Uh, lane, bad);
+    mf_pivot<H, 0, PW, KD>(a, uq, 0.0, rcp_f64(piv), Lf, Uh, lane, bad, Dv);
 }
 
 // The trailing update of panel H on the matrix cores: lower tiles (I, J), I >= J, of tile columns
@@ -2314,8 +2317,8 @@ __device__ __forceinline__ void mf_update(double* M, const double* Lf, const dou
 // tile column T0 that holds panel H + 1's columns and factors panel H + 1 straight away (into the
 // other U buffer), while waves 1-3 update the tile columns past T0 -- disjoint columns of M, so
 // the next pivot chain starts without waiting for the rest of the trailing update.
-template <int NF, int H>
-__device__ __forceinline__ void mf_panel(double* M, double* Lf, double* Up, int tid, bool& bad) {
+template <int NF, int H, bool KD = false>
+__device__ __forceinline__ void mf_panel(double* M, double* Lf, double* Up, int tid, bool& bad, double* Dv = nullptr) {
     constexpr int NT = MfDims<NF>::NT, NH = MfDims<NF>::NH;
     constexpr int C0 = kMfPanel * H;
     const int lane = tid & 63, wave = tid >> 6;
@@ -2328,13 +2331,13 @@ __device__ __forceinline__ void mf_panel(double* M, double* Lf, double* Up, int 
             mf_update<NF, H>(M, Lf, Uh, lane, 0, 1, T0, T0 + 1);
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // the column's updates before its reads
             __builtin_amdgcn_wave_barrier();
-            mf_factor<NF, H + 1>(M, Lf, Up + ((H + 1) & 1) * kMfPanel * kMfLd, lane, bad);
+            mf_factor<NF, H + 1, KD>(M, Lf, Up + ((H + 1) & 1) * kMfPanel * kMfLd, lane, bad, Dv);
         } else {
             mf_update<NF, H>(M, Lf, Uh, lane, wave - 1, kK5Threads / 64 - 1, T0 + 1, NT);
         }
         __syncthreads();
         if constexpr (H == 0) STAMP(13); else if constexpr (H == 2) STAMP(19); else if constexpr (H == 4) STAMP(31);
-        mf_panel<NF, H + 1>(M, Lf, Up, tid, bad);
+        mf_panel<NF, H + 1, KD>(M, Lf, Up, tid, bad, Dv);
     }
 }
 
@@ -2453,10 +2456,10 @@ __device__ __forceinline__ void bk_update(double* M, const double* Uk, int lane,
 // Block step K.  a: column block K of the chain wave's rows (updated); U: 2 x 6 x LD doubles
 // (blocks alternate); Dsc / Lsc: 36 doubles each of chain-wave scratch.  Every wave of the block
 // runs every step (one barrier each).
-template <int NF, int K, int NW>
+template <int NF, int K, int NW, bool KD = false>
 __device__ __forceinline__ void bk_steps(double* M, double* U, double* Dsc, double* Lsc,
                                          double (&a)[BkDims<NF>::RPL][6], int tid, bool& bad,
-                                         const unsigned char* env) {
+                                         const unsigned char* env, double* Dv = nullptr) {
     using D = BkDims<NF>;
     constexpr int RPL = D::RPL, LD = D::LD, c0 = 6 * K;
     const int lane = tid & 63, wave = tid >> 6;
@@ -2503,6 +2506,10 @@ __device__ __forceinline__ void bk_steps(double* M, double* U, double* Dsc, doub
 #pragma unroll
                 for (int i2 = j + 1; i2 <= i; ++i2) Dg[i][i2] = fma(-Lg[i][j], Dg[i2][j], Dg[i][i2]);
         }
+        if constexpr (KD)  // 1 / d kept (the covariance inverts the factor)
+            if (lane == 0)
+#pragma unroll
+                for (int j = 0; j < 6; ++j) Dv[c0 + j] = inv[j];
         // the rows' multipliers, L and U stores, the next block's L rows to Lsc
 #pragma unroll
         for (int h = 0; h < RPL; ++h) {
@@ -2565,16 +2572,16 @@ __device__ __forceinline__ void bk_steps(double* M, double* U, double* Dsc, doub
     } else {
         bk_update<NF, K, NW - 1>(M, U + (K & 1) * 6 * LD, lane, wave - 1, env[K]);
     }
-    if constexpr (K + 1 < NF) bk_steps<NF, K + 1, NW>(M, U, Dsc, Lsc, a, tid, bad, env);
+    if constexpr (K + 1 < NF) bk_steps<NF, K + 1, NW, KD>(M, U, Dsc, Lsc, a, tid, bad, env, Dv);
 }
 
 // The whole factorisation (every wave of the block); afterwards M's columns hold L (unit lower)
 // and row NP holds z.  U: 2 x 6 x LD doubles, S: 72 doubles of scratch.  (A rolled loop over
 // the steps -- one step's code reused instead of ~37 KB of straight-line code -- measured
 // slower: 17.1 vs 13.9 us per K5 launch at config 3, profiles/r05d_k5_stamps.txt.)
-template <int NF, int NW>
+template <int NF, int NW, bool KD = false>
 __device__ __forceinline__ void bk_factor(double* M, double* U, double* S, int tid, bool& bad,
-                                          const unsigned char* env) {
+                                          const unsigned char* env, double* Dv = nullptr) {
     using D = BkDims<NF>;
     double a[D::RPL][6];
     if ((tid >> 6) == 0) {
@@ -2586,7 +2593,7 @@ __device__ __forceinline__ void bk_factor(double* M, double* U, double* S, int t
             for (int j = 0; j < 6; ++j) a[h][j] = M[j * D::LD + r];
         }
     }
-    bk_steps<NF, 0, NW>(M, U, S, S + 36, a, tid, bad, env);
+    bk_steps<NF, 0, NW, KD>(M, U, S, S + 36, a, tid, bad, env, Dv);
 }
 
 template <int NF, bool LL = false>
@@ -4157,6 +4164,7 @@ __global__ __launch_bounds__(256) void ba_p2p_trial(Geometry G, Prob Pr, Work Wk
 
 // landmark triangulation and the depth / reprojection gate (ba_landmarks<TRI>)
 #include "ba_landmarks.hpp"
+#include "ba_covariance.hpp"
 
 }  // namespace
 
@@ -4493,6 +4501,15 @@ struct BundleAdjuster {
     hipEvent_t ev_sel = nullptr;
     bool sel_pending = false;
     bool at_initial = false;  // no solve has started since set_problem: the current state is the initial one
+    // covariance (ba_covariance.hpp), allocated by the first call: Sigma_cc | landmark rows | cost,
+    // the landmark flags, the status words, the chain's own LM state and its timing events
+    DevBuf<double> d_cov;
+    DevBuf<unsigned char> d_cov_flags;
+    DevBuf<int> d_cov_st;
+    DevBuf<LmState> d_cov_state;
+    hipEvent_t ev_cov0 = nullptr, ev_cov1 = nullptr;
+    std::vector<double> cov_host, cov_lm_host;
+    std::vector<unsigned char> cov_flags_host;
 
     void init(const rsvio_ba_params& p) {
         P = p;
@@ -4572,6 +4589,8 @@ struct BundleAdjuster {
         if (gd.ev_launch) (void)hipEventDestroy(gd.ev_launch);
         if (ev_desc) (void)hipEventDestroy(ev_desc);
         if (ev_sel) (void)hipEventDestroy(ev_sel);
+        if (ev_cov0) (void)hipEventDestroy(ev_cov0);
+        if (ev_cov1) (void)hipEventDestroy(ev_cov1);
         if (stream && own_stream) (void)hipStreamDestroy(stream);
     }
 
@@ -5657,6 +5676,148 @@ struct BundleAdjuster {
         }
     }
 
+    // Pose and landmark covariance at the state get_state would return (ba_covariance.hpp).  The
+    // chain relinearises that state into raw buffer 0 -- scratch between solves: every start
+    // linearises the initial state into it again -- by K4 itself, handed x as its initial state and
+    // scratch as the state buffers, LM state and stamp its folded-in reset writes; K4c then runs
+    // on an LM state of the call's own {lambda 0, nothing pending}.  So neither the state buffers
+    // nor the handle's LM states are written.  The outputs are copied out only on a positive status.
+    void covariance(double huber_delta, double* cov_cc, double* cov_pose, const int32_t* lm_idx, int32_t n_sel,
+                    double* cov_lm, uint8_t* lm_flags, rsvio_cov_info* info) {
+        if (pend.active) throw CallOrderError("covariance: a solve is in flight (call rsvio_ba_wait first)");
+        if (sharded()) throw CallOrderError("covariance: not available on a landmark-sharded handle");
+        if (!has_problem) throw std::invalid_argument("covariance: no problem uploaded");
+        if (!(huber_delta > 0.0)) throw std::invalid_argument("covariance: huber_delta must be positive");
+        const int n_lm = G.n_lm, n_kf = G.n_kf, n = 6 * G.n_free;
+        if (n_sel < 0 || (n_sel > 0 && (!cov_lm || !lm_flags)) || (!lm_idx && n_sel != 0 && n_sel != n_lm))
+            throw std::invalid_argument("covariance: landmark selection and its outputs do not match");
+        if (lm_idx)
+            for (int i = 0; i < n_sel; ++i)
+                if (lm_idx[i] < 0 || lm_idx[i] >= n_lm) throw std::invalid_argument("covariance: lm_idx out of range");
+        settle();
+        if (!ev_cov0) {
+            RSVIO_HIP(hipEventCreate(&ev_cov0));
+            RSVIO_HIP(hipEventCreate(&ev_cov1));
+            d_cov_st.alloc(2);
+            d_cov_state.alloc(2);
+            LmState s0{};
+            s0.nu = 2.0;
+            const LmState two[2] = {s0, s0};
+            RSVIO_HIP(hipMemcpy(d_cov_state.p, two, sizeof(two), hipMemcpyHostToDevice));
+        }
+        // Sigma_cc | landmark rows | cost | K4's reset targets: poses, points, 2 stamps
+        const size_t n_res = (size_t)n * n + (size_t)9 * std::max(n_lm, 1) + 1;
+        const size_t n_out = n_res + (size_t)7 * n_kf + (size_t)3 * std::max(n_lm, 1) + 2;
+        grow(d_cov, n_out);
+        grow(d_cov_flags, (size_t)std::max(n_lm, 1));
+        const unsigned char* d_sel = nullptr;
+        if (n_lm && (lm_idx || n_sel == 0)) {
+            if (sel_pending) RSVIO_HIP(hipEventSynchronize(ev_sel));
+            sel_pending = false;
+            std::memset(h_lm_sel.p, 0, (size_t)n_lm);
+            for (int i = 0; i < n_sel; ++i) h_lm_sel.p[lm_idx[i]] = 1;
+            d_sel = h_lm_sel_dev;
+        }
+        Work wk = work_at(0);
+        const double *pose = wk.pose_init, *pw = wk.pw_init;
+        if (!state_fresh) {
+            const int cur = h_state.p->cur;
+            pose = wk.pose[cur];
+            pw = wk.pw[cur];
+        }
+        // K4 (reset folded in): "initial" state x, both state buffers and the stamp in scratch
+        Work wl = wk;
+        wl.pose_init = pose;
+        wl.pw_init = pw;
+        wl.pose[0] = wl.pose[1] = d_cov.p + n_res;
+        wl.pw[0] = wl.pw[1] = wl.pose[0] + (size_t)7 * n_kf;
+        wl.tick = reinterpret_cast<unsigned long long*>(wl.pw[0] + (size_t)3 * std::max(n_lm, 1));
+        wl.st = d_cov_state.p + 1;
+        wl.st_prev = wl.st;
+        // K4c and the covariance kernels: x as both state buffers, raw buffer 0
+        wk.pose[0] = wk.pose[1] = const_cast<double*>(pose);
+        wk.pw[0] = wk.pw[1] = const_cast<double*>(pw);
+        wk.raws[1] = wk.raws[0];
+        wk.rawl[1] = wk.rawl[0];
+        wk.st_prev = d_cov_state.p;
+        wk.st = d_cov_state.p + 1;
+        Geometry Gc = G;
+        Gc.huber_delta = huber_delta;
+        Gc.chol = 0;
+        const Prob pr = prob();
+        CovOut O;
+        O.cc = d_cov.p;
+        O.lm = d_cov.p + (size_t)n * n;
+        O.cost = O.lm + (size_t)9 * std::max(n_lm, 1);
+        O.flags = d_cov_flags.p;
+        O.cst = d_cov_st.p;
+        settled = false;
+        RSVIO_HIP(hipMemsetAsync(d_cov_st.p, 0, 2 * sizeof(int), stream));
+        RSVIO_HIP(hipEventRecord(ev_cov0, stream));
+        if (G.n_wave) hipLaunchKernelGGL(ba_linearize, dim3(G.n_wave), dim3(64), 0, stream, Gc, pr, wl, 0.0);
+        hipLaunchKernelGGL(ba_schur_chunks, dim3(G.n_chunk), dim3(kSchurThreads), 0, stream, Gc, pr, wk,
+                           LmArgs{1, 0.0, 0.0}, 0);
+        {
+            const dim3 g(1), b(kK5Threads), b3(64 * kBkWaves);
+            switch (G.n_free <= 10 ? G.n_free : bk_template_nf(G.n_free)) {
+#define RSVIO_COVC(NF) \
+    case NF: hipLaunchKernelGGL(ba_camera_covariance<NF>, g, NF <= 10 ? b : b3, 0, stream, Gc, pr, wk, O); break;
+                RSVIO_COVC(1) RSVIO_COVC(2) RSVIO_COVC(3) RSVIO_COVC(4) RSVIO_COVC(5)
+                RSVIO_COVC(6) RSVIO_COVC(7) RSVIO_COVC(8) RSVIO_COVC(9) RSVIO_COVC(10)
+                RSVIO_COVC(13) RSVIO_COVC(16) RSVIO_COVC(20)
+#undef RSVIO_COVC
+                default: break;
+            }
+        }
+        hipLaunchKernelGGL(ba_landmark_covariance, dim3(std::max(G.n_wave + (n_lm + 63) / 64, 1)), dim3(64), 0, stream,
+                           Gc, pr, wk, reinterpret_cast<const unsigned long long*>(d_arena.p + lay.mask), d_sel, O);
+        RSVIO_HIP(hipGetLastError());
+        RSVIO_HIP(hipEventRecord(ev_cov1, stream));
+        RSVIO_HIP(hipMemsetAsync(d_singular.p, 0, sizeof(int), stream));  // K4c may have set it
+        int cst[2] = {0, 0};
+        double cost = 0.0;
+        RSVIO_HIP(hipMemcpyAsync(cst, d_cov_st.p, sizeof(cst), hipMemcpyDeviceToHost, stream));
+        RSVIO_HIP(hipMemcpyAsync(&cost, O.cost, sizeof(double), hipMemcpyDeviceToHost, stream));
+        RSVIO_HIP(hipStreamSynchronize(stream));
+        float ms = 0.0f;
+        RSVIO_HIP(hipEventElapsedTime(&ms, ev_cov0, ev_cov1));
+        info->n_free = G.n_free;
+        info->n_singular = cst[1];
+        info->reserved = 0;
+        info->cost = cost;
+        info->device_ms = ms;
+        info->status = cst[1] > 0 ? RSVIO_COV_LANDMARK_SINGULAR : cst[0] == 1 ? RSVIO_COV_OK : RSVIO_COV_CAMERA_SINGULAR;
+        if (info->status == RSVIO_COV_OK) {
+            if (cov_cc || cov_pose) {
+                cov_host.resize((size_t)n * n);
+                RSVIO_HIP(hipMemcpyAsync(cov_host.data(), O.cc, sizeof(double) * cov_host.size(), hipMemcpyDeviceToHost,
+                                         stream));
+            }
+            if (n_sel > 0) {
+                cov_lm_host.resize((size_t)9 * n_lm);
+                cov_flags_host.resize((size_t)n_lm);
+                RSVIO_HIP(hipMemcpyAsync(cov_lm_host.data(), O.lm, sizeof(double) * cov_lm_host.size(),
+                                         hipMemcpyDeviceToHost, stream));
+                RSVIO_HIP(hipMemcpyAsync(cov_flags_host.data(), O.flags, (size_t)n_lm, hipMemcpyDeviceToHost, stream));
+            }
+            RSVIO_HIP(hipStreamSynchronize(stream));
+            if (cov_cc) std::memcpy(cov_cc, cov_host.data(), sizeof(double) * cov_host.size());
+            if (cov_pose)
+                for (int k = 0; k < n_kf; ++k) {
+                    const int f = hs_free[k];
+                    for (int i = 0; i < 6; ++i)
+                        for (int j = 0; j < 6; ++j)
+                            cov_pose[36 * k + 6 * i + j] = f < 0 ? 0.0 : cov_host[(size_t)(6 * f + i) * n + 6 * f + j];
+                }
+            for (int i = 0; i < n_sel; ++i) {
+                const int l = lm_idx ? lm_idx[i] : i;
+                std::memcpy(cov_lm + (size_t)9 * i, cov_lm_host.data() + (size_t)9 * l, 9 * sizeof(double));
+                lm_flags[i] = cov_flags_host[l];
+            }
+        }
+        settled = true;
+    }
+
     void build_system(double lambda, double huber_delta, double* S, double* b, double* cost) {
         require_idle("build_system");
         state_export = false;  // K4 below resets the state buffers
@@ -6011,6 +6172,18 @@ int rsvio_ba_check_landmarks(rsvio_ba* ba, int32_t n_lm, const rsvio_landmark_ga
     if (!gate_ok(gate, "rsvio_ba_check_landmarks")) return RSVIO_ERR_INVALID_ARG;
     return guarded([&] {
         ba->b.landmarks(false, nullptr, n_lm, *gate, nullptr, info_out, n_ok);
+        return (int)RSVIO_OK;
+    });
+}
+
+int rsvio_ba_covariance(rsvio_ba* ba, double huber_delta, double* cov_cc, double* cov_pose, const int32_t* lm_idx,
+                        int32_t n_sel, double* cov_lm, uint8_t* lm_flags, rsvio_cov_info* info) {
+    if (!ba || !info) {
+        rsvio::set_last_error("rsvio_ba_covariance: null handle or info");
+        return RSVIO_ERR_INVALID_ARG;
+    }
+    return guarded([&] {
+        ba->b.covariance(huber_delta, cov_cc, cov_pose, lm_idx, n_sel, cov_lm, lm_flags, info);
         return (int)RSVIO_OK;
     });
 }

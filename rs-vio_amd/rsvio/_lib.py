@@ -88,6 +88,12 @@ class LandmarkInfo(C.Structure):
                 ("max_depth", C.c_double), ("max_sq_error", C.c_double)]
 
 
+class CovInfo(C.Structure):
+    """rsvio_cov_info (32 B): the outcome of rsvio_ba_covariance."""
+    _fields_ = [("status", C.c_int32), ("n_free", C.c_int32), ("n_singular", C.c_int32), ("reserved", C.c_int32),
+                ("cost", C.c_double), ("device_ms", C.c_double)]
+
+
 # the same record as a numpy dtype (info arrays are filled in place by the library)
 LANDMARK_INFO_DTYPE = [("n_obs", "<i4"), ("flags", "<i4"), ("min_depth", "<f8"), ("max_depth", "<f8"),
                        ("max_sq_error", "<f8")]
@@ -175,6 +181,7 @@ SIG = {
     "rsvio_ba_get_state": (C.c_int, [P, P, P]),
     "rsvio_ba_triangulate": (C.c_int, [P, P, C.c_int32, C.POINTER(LandmarkGate), P, P, C.POINTER(C.c_int32)]),
     "rsvio_ba_check_landmarks": (C.c_int, [P, C.c_int32, C.POINTER(LandmarkGate), P, C.POINTER(C.c_int32)]),
+    "rsvio_ba_covariance": (C.c_int, [P, C.c_double, P, P, P, C.c_int32, P, P, C.POINTER(CovInfo)]),
     "rsvio_ba_build_system": (C.c_int, [P, C.c_double, C.c_double, P, P, C.POINTER(C.c_double)]),
     "rsvio_rccl_unique_id": (C.c_int, [P, C.c_size_t]),
     "rsvio_ba_attach_comm": (C.c_int, [P, C.c_int32, C.c_int32, P]),

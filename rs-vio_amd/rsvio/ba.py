@@ -48,6 +48,28 @@ TRI_ALL_VIEWS, TRI_FIRST_STEREO = 0, 1      # RSVIO_TRI_*
 LM_OK, LM_TOO_FEW, LM_DEGENERATE, LM_DEPTH, LM_ERROR, LM_NOT_SELECTED = 1, 2, 4, 8, 16, 32   # RSVIO_LM_* flags
 
 
+COV_OK, COV_CAMERA_SINGULAR, COV_LANDMARK_SINGULAR = 1, -1, -2   # RSVIO_COV_* (Covariance.status)
+COV_LM_OK, COV_LM_NOT_OBSERVED = 1, 2                              # RSVIO_COV_LM_* (Covariance.flags)
+
+
+@dataclass
+class Covariance:
+    """The result of BundleAdjuster.covariance, in normalised-image-coordinate^2 per unit
+    measurement variance: pose (n_kf x 6 x 6, each keyframe's block in the [dt; dw] tangent of
+    T_B_W, zeros for a fixed keyframe), full (n x n over the free keyframes in ascending order, or
+    None), landmarks (n_sel x 3 x 3 or None) with flags (COV_LM_*).  On a negative status the
+    arrays are None."""
+    status: int
+    pose: np.ndarray | None
+    full: np.ndarray | None
+    landmarks: np.ndarray | None
+    flags: np.ndarray | None
+    cost: float
+    device_ms: float
+    n_free: int = 0
+    n_singular: int = 0
+
+
 def landmark_gate(mode=TRI_FIRST_STEREO, min_depth=0.1, max_depth=100.0, max_sq_error=0.0):
     """rsvio_landmark_gate; the defaults: the first stereo pair, the reference configs' `depth:`
     section (min_depth 0.1, max_depth 100.0, read by nothing there), the error bound off."""
@@ -281,6 +303,36 @@ class BundleAdjuster:
         check(_lib.load().rsvio_ba_check_landmarks(self._h, self.n_lm, C.byref(g), ptr(info), C.byref(n)))
         return info, n.value
 
+    def covariance(self, landmarks=None, full=False, huber_delta=2.0):
+        """rsvio_ba_covariance at the state state() would return: the pose covariance S^-1 of the
+        reduced camera system at lambda = 0 and, per landmark, V^-1 + sum Y_a^T Sigma_cc[a,b] Y_b,
+        in normalised-image-coordinate^2 per unit measurement variance (multiply by sigma^2).
+        landmarks: None (none), True (all) or an index array (repeats allowed); full: also the
+        n x n matrix over the free keyframes.  Returns a Covariance; on a negative status
+        (COV_CAMERA_SINGULAR, COV_LANDMARK_SINGULAR) its arrays are None."""
+        if landmarks is None or landmarks is False:
+            idx, n_sel = None, 0
+        elif landmarks is True:
+            idx, n_sel = None, self.n_lm
+        else:
+            idx = _c(np.asarray(landmarks).reshape(-1), np.int32)
+            n_sel = len(idx)
+        pose = np.zeros((self.n_kf, 6, 6))
+        cc = np.zeros(120 * 120) if full else None  # n = 6 n_free <= 120; info.n_free says which
+        lm = np.zeros((n_sel, 3, 3)) if n_sel else None
+        flags = np.zeros(n_sel, np.uint8) if n_sel else None
+        info = _lib.CovInfo()
+        check(_lib.load().rsvio_ba_covariance(self._h, huber_delta, ptr(cc), ptr(pose), ptr(idx), n_sel, ptr(lm),
+                                              ptr(flags), C.byref(info)))
+        ok = info.status == COV_OK
+        if full and ok:
+            n = 6 * info.n_free
+            cc = cc[:n * n].reshape(n, n).copy()
+        if landmarks is not None and landmarks is not False and n_sel == 0:
+            lm, flags = np.zeros((0, 3, 3)), np.zeros(0, np.uint8)
+        return Covariance(info.status, pose if ok else None, cc if ok else None, lm if ok else None,
+                          flags if ok else None, info.cost, info.device_ms, info.n_free, info.n_singular)
+
     def build_system(self, lam, huber_delta=2.0):
         nfree = int((self._keep[1] == 0).sum())
         S = np.zeros((6 * nfree, 6 * nfree))
@@ -404,12 +456,16 @@ class SlidingWindow:
     """Keyframe FIFO + BA problem assembly (sliding_window.rs:21-486) over the GPU solver."""
 
     def __init__(self, max_frames: int, device: int = 0, solver: BundleAdjuster | None = None,
-                 landmark_init: str = "ray", gate=None, cull: bool = False):
+                 landmark_init: str = "ray", gate=None, cull: bool = False, covariance: bool = False):
         """landmark_init: "ray" (the reference's rule: a landmark that is not in the map starts at
         depth 2.0 along its first observation's ray) or "triangulate" (those landmarks are
         triangulated on the device from the window's initial poses; one the gate rejects keeps the
         ray value).  cull: after a successful solve, landmarks the gate rejects on the solved state
-        are left out of the new map.  gate: landmark_gate(...), default landmark_gate()."""
+        are left out of the new map.  gate: landmark_gate(...), default landmark_gate().
+        covariance: after a successful optimize / finish, pose_covariance (n_kf x 6 x 6, in window
+        order) and landmark_covariance (feature id -> 3 x 3) of the applied state are kept, per unit
+        measurement variance (BundleAdjuster.covariance); None when the call reports a singular
+        system.  Off by default, and nothing changes when off."""
         if landmark_init not in ("ray", "triangulate"):
             raise ValueError('landmark_init must be "ray" or "triangulate"')
         self.max_frames = max_frames
@@ -423,7 +479,11 @@ class SlidingWindow:
         self.fallbacks = 0                             # SparseCholesky retries (diagnostic)
         self.solver = solver or BundleAdjuster(max_keyframes=max(max_frames, 2), device=device)
         self.landmark_init, self.gate, self.cull = landmark_init, gate, bool(cull)
-        need = (("triangulate",) if landmark_init == "triangulate" else ()) + (("check_landmarks",) if cull else ())
+        self.covariance = bool(covariance)
+        self.pose_covariance = None
+        self.landmark_covariance = None
+        need = ((("triangulate",) if landmark_init == "triangulate" else ()) + (("check_landmarks",) if cull else ())
+                + (("covariance",) if covariance else ()))
         for name in need + (("set_problem", "run", "state") if need else ()):
             if not hasattr(self.solver, name):
                 raise ValueError(f"landmark_init / cull need a solver with {name}()")
@@ -514,7 +574,7 @@ class SlidingWindow:
                 self.fallbacks += 1
                 res = self.solver.run(fallback_cfg(cfg))
             pose, pw = self.solver.state()
-            return self._apply(*self._culled(ids, pose, pw, res))
+            return self._with_covariance(ids, cfg, self._apply(*self._culled(ids, pose, pw, res)))
         pose, pw, res = self.solver.solve(pose7, fixed, p_init, lm, kf, cam, uv, tcb, cfg)
         if res.status == LINEAR_SOLVE_FAILED:
             # sliding_window.rs:326-353: a singular Schur solve is retried from the same initial
@@ -524,7 +584,20 @@ class SlidingWindow:
         return self._apply(ids, pose, pw, res)
 
     def _split(self) -> bool:
-        return self.landmark_init == "triangulate" or self.cull
+        return self.landmark_init == "triangulate" or self.cull or self.covariance
+
+    def _with_covariance(self, ids, cfg, ok):
+        """covariance=True: after a solve that was applied, the covariance of the applied state (the
+        solver still holds it) at the solve's Huber delta; passes `ok` through."""
+        if self.covariance and ok:
+            cov = self.solver.covariance(landmarks=True, huber_delta=cfg.huber_delta if cfg else 2.0)
+            if cov.status == COV_OK:
+                self.pose_covariance = cov.pose
+                seen = cov.flags == COV_LM_OK
+                self.landmark_covariance = dict(zip(np.asarray(ids)[seen].tolist(), cov.landmarks[seen]))
+            else:
+                self.pose_covariance = self.landmark_covariance = None
+        return ok
 
     def _new_mask(self, ids) -> np.ndarray:
         """One byte per landmark: 1 where its id is not in the map (the landmarks the reference
@@ -606,4 +679,4 @@ class SlidingWindow:
             self.fallbacks += 1
             res = self.solver.run(fallback_cfg(cfg))
         pose, pw = self.solver.state()
-        return self._apply(*self._culled(ids, pose, pw, res))
+        return self._with_covariance(ids, cfg, self._apply(*self._culled(ids, pose, pw, res)))
