@@ -572,6 +572,73 @@ int rsvio_track_motion_tracker(rsvio_pnp* p, rsvio_tracker* t, const double* T_W
                                const double* T_C_B2, const rsvio_lm_cfg* cfg,
                                const rsvio_keyframe_rule* rule, rsvio_motion_result* res);
 
+/* Outlier-robust motion tracking: a stereo 3-point RANSAC in front of the same LM (no reference
+ * counterpart: the reference's only defence is Huber(2.0) in normalised units, inactive for real
+ * residuals).  Three launches on the handle's stream, no host wait between them and no workgroup
+ * waiting on another; every cross-workgroup reduction is done by the next launch.
+ *   R1  the joined observations (a feature whose id is in the map; left list then right list, each
+ *       in list order -- the order of rsvio_track_motion's factors) and the PAIRS: ids present in
+ *       both lists with a map point, by ascending position in the left list (equal ids inside the
+ *       right list: the first).  Each pair's point q in the BODY frame is the least-squares
+ *       intersection of its two rays ([R | t] = T_C_B[c], c_o = -R^T t, d_o = R^T (u, v, 1)^T / |.|,
+ *       M_o = I - d_o d_o^T, q = (sum M_o)^-1 sum M_o c_o); the pair is valid iff
+ *       det(sum M_o) > 1e-12 2^3 (rsvio_ba_triangulate's rule at two rays), q is finite and both
+ *       depths (T_C_B[c] q)_z >= min_depth.
+ *   R2  hypotheses 0 <= h < n_hyp <= 1024, one wave each.  h = 0 is the prior: the pose
+ *       rsvio_track_motion starts from.  h >= 1 takes pair indices i_k, k = 0..2, from
+ *       samples[3 h + k] (row 0 is ignored) or, with samples NULL, i_k = z mod n_pairs in 64-bit
+ *       unsigned arithmetic with  z = seed + 0x9E3779B97F4A7C15 (3 h + k + 1),
+ *       z = (z ^ z >> 30) 0xBF58476D1CE4E5B9,  z = (z ^ z >> 27) 0x94D049BB133111EB,  z ^= z >> 31.
+ *       With a = w2 - w1, b = w3 - w1, e1 = a / |a|, e3 = a x b / |a x b|, e2 = e3 x e1 and
+ *       F_w = [e1 e2 e3] of the three map points, F_q likewise of the three q:  R = F_q F_w^T,
+ *       t = mean(q) - R mean(w)  (T_B_W).  The hypothesis is invalid (count -1) when n_pairs < 3, an
+ *       index is out of range (not an error), two indices are equal, a chosen pair is invalid,
+ *       |a x b|^2 <= 1e-12 |a|^2 |b|^2 in either frame, or anything is not finite.  A joined
+ *       observation is an inlier iff p_C = T_C_B[c] (R w + t) has z >= min_depth and
+ *       |p_C.xy / z - uv|^2 <= inlier_sq_error; hyp_count[h] is the number of inliers.
+ *   R3  the winner is the largest count, the lowest h on a tie.  Below max(min_inliers, 1):
+ *       ransac_status = NO_CONSENSUS and `motion` is what rsvio_track_motion returns when no
+ *       feature has a map point (RSVIO_LM_SKIPPED, identity, is_keyframe = 1); every joined
+ *       observation is marked an outlier.  Otherwise rsvio_track_motion's LM (the caller's cfg) runs
+ *       on the winner's inliers only, in the same factor order, from the winner's pose, and the
+ *       keyframe rule is applied against T_W_B_last_kf; motion.n_observations is the number of
+ *       factors.  Then every joined observation is classified by the same test at the refined pose
+ *       (at the winner's pose if the LM failed): mask_l[n_l], mask_r[n_r] hold 0 = no map point,
+ *       1 = inlier, 2 = outlier, n_inliers the number of 1s.
+ * n_hyp = 1 with an all-accepting inlier_sq_error (e.g. 1e300) and min_inliers <= the joined
+ * observations gives rsvio_track_motion's result bit for bit.  TOO_FEW_PAIRS (n_pairs < 3: only
+ * h = 0 could be valid) is a success status.  device_ms: the three launches by HIP events.  Two calls
+ * give identical bits (the counts are integers, every floating-point sum runs in a fixed order).
+ * n_hyp outside [1, 1024], inlier_sq_error <= 0 or NaN, or a NULL cfg: RSVIO_ERR_INVALID_ARG. */
+enum { RSVIO_RANSAC_OK = 1, RSVIO_RANSAC_TOO_FEW_PAIRS = 2, RSVIO_RANSAC_NO_CONSENSUS = -1 };
+typedef struct {
+    int32_t n_hyp, min_inliers;
+    uint64_t seed;
+    double inlier_sq_error;  /* squared normalised reprojection error (1e-4: ~4.6 px at EuRoC's fx) */
+    double min_depth;        /* metres along the optical axis (the reference configs: 0.1) */
+} rsvio_ransac_cfg;          /* 32 bytes */
+typedef struct {
+    rsvio_motion_result motion;
+    int32_t ransac_status;   /* RSVIO_RANSAC_* */
+    int32_t n_pairs, n_valid_pairs, n_valid_hyp, best_hyp, best_count, n_inliers, reserved;
+    double device_ms;
+} rsvio_robust_motion_result;  /* 224 bytes */
+int rsvio_track_motion_robust(rsvio_pnp* p, const uint64_t* ids_l, const float* uv_l, size_t n_l,
+                              const uint64_t* ids_r, const float* uv_r, size_t n_r,
+                              const double* T_W_B_last_kf, const double* T_C_B2, const rsvio_lm_cfg* cfg,
+                              const rsvio_keyframe_rule* rule, const rsvio_ransac_cfg* ransac,
+                              const int32_t* samples,  /* n_hyp x 3 pair indices, or NULL: the seeded sampler */
+                              uint8_t* mask_l, uint8_t* mask_r,  /* n_l, n_r, or NULL */
+                              int32_t* hyp_count,      /* n_hyp, or NULL */
+                              rsvio_robust_motion_result* res);
+/* Same for the tracker's last collected frame, read in place on the device (as
+ * rsvio_track_motion_tracker); mask_l / mask_r are indexed like the collected feature lists. */
+int rsvio_track_motion_robust_tracker(rsvio_pnp* p, rsvio_tracker* t, const double* T_W_B_last_kf,
+                                      const double* T_C_B2, const rsvio_lm_cfg* cfg,
+                                      const rsvio_keyframe_rule* rule, const rsvio_ransac_cfg* ransac,
+                                      const int32_t* samples, uint8_t* mask_l, uint8_t* mask_r,
+                                      int32_t* hyp_count, rsvio_robust_motion_result* res);
+
 #ifdef __cplusplus
 }
 #endif

@@ -644,6 +644,8 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_track_motion_kernel(PnpArgs A
     STAMP(29);
 }
 
+#include "pnp_robust.hpp"
+
 }  // namespace
 
 RSVIO_DBG_READER(rsvio_dbg_pnp_stamps)
@@ -666,6 +668,27 @@ struct Pnp {
     double wclk_khz = 1.0e5;
     double q0_key[16] = {};              // T_W_B_last_kf of the cached initial quaternion
     double q0[4] = {1.0, 0.0, 0.0, 0.0};
+    // the robust path's scratch (pnp_robust.hpp), allocated by its first call
+    DevBuf<double> rdbl;                 // w, uv, pair_q, pair_w, hyp_pose
+    DevBuf<int> rint;                    // cam, pos, pair_ok, counts, hyp_count, samples
+    DevBuf<uint8_t> rmask;
+    HostBuf<rsvio_robust_motion_result> hrobust;
+    HostBuf<int> hrint;                  // samples (staging), hyp_count (read back)
+    HostBuf<uint8_t> hrmask;
+    hipEvent_t rev[2] = {nullptr, nullptr};
+
+    void init_robust() {
+        if (rev[1]) return;
+        constexpr size_t cap = kPnpMaxFeatures;
+        rdbl.alloc(11 * cap + 12 * kRansacMaxHyp);
+        rint.alloc(3 * cap + 4 + 4 * kRansacMaxHyp);
+        rmask.alloc(cap);
+        hrobust.alloc(1);
+        hrint.alloc(4 * kRansacMaxHyp);
+        hrmask.alloc(cap);
+        RSVIO_HIP(hipEventCreate(&rev[0]));
+        RSVIO_HIP(hipEventCreate(&rev[1]));
+    }
 
     void init(int dev) {
         device = dev;
@@ -678,6 +701,8 @@ struct Pnp {
         (void)hipGetLastError();
     }
     ~Pnp() {
+        for (hipEvent_t e : rev)
+            if (e) (void)hipEventDestroy(e);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -747,6 +772,127 @@ int run_pnp(Pnp& p, const PnpArgs& A, hipStream_t stream, rsvio_motion_result* r
         set_last_error("track_motion: more than 4096 features in one frame");
         return RSVIO_ERR_CAPACITY;
     }
+    return RSVIO_OK;
+}
+
+// A frame given as host arrays: staged and uploaded on the handle's stream, A's lists set to it
+void host_frame(Pnp& P, const uint64_t* ids_l, const float* uv_l, size_t n_l, const uint64_t* ids_r,
+                const float* uv_r, size_t n_r, PnpArgs& A) {
+    const size_t n = n_l + n_r, bytes = n * 16;
+    if (P.feat.n < bytes || !P.feat.p) {
+        const size_t cap = (size_t)kPnpMaxFeatures * 16;
+        P.feat.alloc(cap);
+        P.hfeat.alloc(cap);
+    }
+    uint8_t* hb = P.hfeat.p;
+    if (n_l) std::memcpy(hb, ids_l, 8 * n_l);
+    if (n_r) std::memcpy(hb + 8 * n_l, ids_r, 8 * n_r);
+    if (n_l) std::memcpy(hb + 8 * n, uv_l, 8 * n_l);
+    if (n_r) std::memcpy(hb + 8 * n + 8 * n_l, uv_r, 8 * n_r);
+    if (n) RSVIO_HIP(hipMemcpyAsync(P.feat.p, hb, bytes, hipMemcpyHostToDevice, P.active()));
+    A.ids[0] = P.feat.p;
+    A.ids[1] = P.feat.p + 8 * n_l;
+    A.id_stride = 8;
+    A.uv[0] = reinterpret_cast<const float2*>(P.feat.p + 8 * n);
+    A.uv[1] = reinterpret_cast<const float2*>(P.feat.p + 8 * n + 8 * n_l);
+    A.dcount = nullptr;
+    A.n[0] = (int)n_l;
+    A.n[1] = (int)n_r;
+}
+
+// The tracker's last collected frame, read in place: A's lists set to its output slot
+int tracker_frame(Pnp& P, rsvio_tracker* t, PnpArgs& A) {
+    const TrackerView v = tracker_view(t);
+    if (!v.undist[0]) {
+        set_last_error("rsvio_track_motion_tracker: attach cameras to the tracker first");
+        return (int)RSVIO_ERR_INVALID_ARG;
+    }
+    if (v.device != P.device) {
+        set_last_error("rsvio_track_motion_tracker: tracker and pnp handle on different devices");
+        return (int)RSVIO_ERR_INVALID_ARG;
+    }
+    RSVIO_HIP(hipSetDevice(P.device));
+    if (v.n[0] + v.n[1] > kPnpMaxFeatures) {
+        set_last_error("track_motion: more than 4096 features in one frame");
+        return (int)RSVIO_ERR_CAPACITY;
+    }
+    // the map upload (set_map) is ordered before this launch: it synchronised its stream.  The
+    // view is the last collected frame's output slot, complete on the device (its collect
+    // waited for it), so the launch goes on the handle's own stream: it runs beside a next
+    // frame already submitted to the tracker's stream, which writes the other slot
+    A.ids[0] = reinterpret_cast<const uint8_t*>(v.out[0]);
+    A.ids[1] = reinterpret_cast<const uint8_t*>(v.out[1]);
+    A.id_stride = (int)sizeof(rsvio_feature);
+    A.uv[0] = v.undist[0];
+    A.uv[1] = v.undist[1];
+    A.dcount = nullptr;
+    A.n[0] = v.n[0];
+    A.n[1] = v.n[1];
+    return (int)RSVIO_OK;
+}
+
+bool ransac_cfg_ok(const rsvio_ransac_cfg* rc) {
+    return rc && rc->n_hyp >= 1 && rc->n_hyp <= kRansacMaxHyp && rc->inlier_sq_error > 0.0;  // (NaN fails >)
+}
+
+// The three launches of pnp_robust.hpp on `stream`, then the one host wait; A holds the feature
+// lists (device pointers and counts, n_l + n_r <= kPnpMaxFeatures)
+int run_pnp_robust(Pnp& p, PnpArgs A, hipStream_t stream, const rsvio_ransac_cfg* rc, const int32_t* samples,
+                   uint8_t* mask_l, uint8_t* mask_r, int32_t* hyp_count, rsvio_robust_motion_result* res) {
+    p.init_robust();
+    constexpr size_t cap = kPnpMaxFeatures;
+    const int n_l = A.n[0], n_r = A.n[1];
+    RobustArgs RA{};
+    A.out = &p.hrobust.p->motion;
+    RA.P = A;
+    double* d = p.rdbl.p;
+    RA.B.w = d;
+    RA.B.uv = d + 3 * cap;
+    RA.B.pair_q = d + 5 * cap;
+    RA.B.pair_w = d + 8 * cap;
+    RA.B.hyp_pose = d + 11 * cap;
+    int* q = p.rint.p;
+    RA.B.cam = q;
+    RA.B.pos = q + cap;
+    RA.B.pair_ok = q + 2 * cap;
+    RA.B.counts = q + 3 * cap;
+    RA.B.hyp_count = q + 3 * cap + 4;
+    int* d_samples = q + 3 * cap + 4 + kRansacMaxHyp;
+    RA.B.samples = nullptr;
+    RA.B.mask = p.rmask.p;
+    RA.n_hyp = rc->n_hyp;
+    RA.min_inliers = rc->min_inliers;
+    RA.seed = rc->seed;
+    RA.inlier_sq = rc->inlier_sq_error;
+    RA.min_depth = rc->min_depth;
+    RA.out = p.hrobust.p;
+    if (samples) {
+        std::memcpy(p.hrint.p, samples, sizeof(int32_t) * 3 * (size_t)rc->n_hyp);
+        RSVIO_HIP(hipMemcpyAsync(d_samples, p.hrint.p, sizeof(int32_t) * 3 * (size_t)rc->n_hyp, hipMemcpyHostToDevice,
+                                 stream));
+        RA.B.samples = d_samples;
+    }
+    RSVIO_HIP(hipEventRecord(p.rev[0], stream));
+    hipLaunchKernelGGL(pnp_robust_join_kernel, dim3(1), dim3(kPnpThreads), 0, stream, RA);
+    hipLaunchKernelGGL(pnp_robust_score_kernel, dim3(rc->n_hyp), dim3(64), 0, stream, RA);
+    hipLaunchKernelGGL(pnp_robust_refit_kernel, dim3(1), dim3(kPnpThreads), 0, stream, RA);
+    RSVIO_HIP(hipGetLastError());
+    RSVIO_HIP(hipEventRecord(p.rev[1], stream));
+    int* h_counts = p.hrint.p + 3 * kRansacMaxHyp;
+    if ((mask_l || mask_r) && n_l + n_r)
+        RSVIO_HIP(hipMemcpyAsync(p.hrmask.p, p.rmask.p, (size_t)(n_l + n_r), hipMemcpyDeviceToHost, stream));
+    if (hyp_count)
+        RSVIO_HIP(hipMemcpyAsync(h_counts, RA.B.hyp_count, sizeof(int32_t) * (size_t)rc->n_hyp, hipMemcpyDeviceToHost,
+                                 stream));
+    RSVIO_HIP(hipStreamSynchronize(stream));
+    *res = *p.hrobust.p;
+    keyframe_rule(A, &res->motion);
+    float ms = 0.f;
+    RSVIO_HIP(hipEventElapsedTime(&ms, p.rev[0], p.rev[1]));
+    res->device_ms = ms;
+    if (mask_l && n_l) std::memcpy(mask_l, p.hrmask.p, (size_t)n_l);
+    if (mask_r && n_r) std::memcpy(mask_r, p.hrmask.p + n_l, (size_t)n_r);
+    if (hyp_count) std::memcpy(hyp_count, h_counts, sizeof(int32_t) * (size_t)rc->n_hyp);
     return RSVIO_OK;
 }
 
@@ -864,27 +1010,8 @@ int rsvio_track_motion(rsvio_pnp* h, const uint64_t* ids_l, const float* uv_l, s
     return guarded([&] {
         auto& P = h->p;
         RSVIO_HIP(hipSetDevice(P.device));
-        const size_t n = n_l + n_r, bytes = n * 16;
-        if (P.feat.n < bytes || !P.feat.p) {
-            const size_t cap = (size_t)rsvio::kPnpMaxFeatures * 16;
-            P.feat.alloc(cap);
-            P.hfeat.alloc(cap);
-        }
-        uint8_t* hb = P.hfeat.p;
-        if (n_l) std::memcpy(hb, ids_l, 8 * n_l);
-        if (n_r) std::memcpy(hb + 8 * n_l, ids_r, 8 * n_r);
-        if (n_l) std::memcpy(hb + 8 * n, uv_l, 8 * n_l);
-        if (n_r) std::memcpy(hb + 8 * n + 8 * n_l, uv_r, 8 * n_r);
-        if (n) RSVIO_HIP(hipMemcpyAsync(P.feat.p, hb, bytes, hipMemcpyHostToDevice, P.active()));
         rsvio::PnpArgs A = rsvio::make_args(P, T_W_B_last_kf, T_C_B2, cfg, rule);
-        A.ids[0] = P.feat.p;
-        A.ids[1] = P.feat.p + 8 * n_l;
-        A.id_stride = 8;
-        A.uv[0] = reinterpret_cast<const float2*>(P.feat.p + 8 * n);
-        A.uv[1] = reinterpret_cast<const float2*>(P.feat.p + 8 * n + 8 * n_l);
-        A.dcount = nullptr;
-        A.n[0] = (int)n_l;
-        A.n[1] = (int)n_r;
+        rsvio::host_frame(P, ids_l, uv_l, n_l, ids_r, uv_r, n_r, A);
         return rsvio::run_pnp(P, A, P.active(), res);
     });
 }
@@ -894,34 +1021,46 @@ int rsvio_track_motion_tracker(rsvio_pnp* h, rsvio_tracker* t, const double* T_W
     if (!h || !t || !T_W_B_last_kf || !T_C_B2 || !cfg || !rule || !res) return RSVIO_ERR_INVALID_ARG;
     return guarded([&] {
         auto& P = h->p;
-        const rsvio::TrackerView v = rsvio::tracker_view(t);
-        if (!v.undist[0]) {
-            rsvio::set_last_error("rsvio_track_motion_tracker: attach cameras to the tracker first");
-            return (int)RSVIO_ERR_INVALID_ARG;
-        }
-        if (v.device != P.device) {
-            rsvio::set_last_error("rsvio_track_motion_tracker: tracker and pnp handle on different devices");
-            return (int)RSVIO_ERR_INVALID_ARG;
-        }
-        RSVIO_HIP(hipSetDevice(P.device));
-        if (v.n[0] + v.n[1] > rsvio::kPnpMaxFeatures) {
-            rsvio::set_last_error("track_motion: more than 4096 features in one frame");
-            return (int)RSVIO_ERR_CAPACITY;
-        }
-        // the map upload (set_map) is ordered before this launch: it synchronised its stream.  The
-        // view is the last collected frame's output slot, complete on the device (its collect
-        // waited for it), so the launch goes on the handle's own stream: it runs beside a next
-        // frame already submitted to the tracker's stream, which writes the other slot
         rsvio::PnpArgs A = rsvio::make_args(P, T_W_B_last_kf, T_C_B2, cfg, rule);
-        A.ids[0] = reinterpret_cast<const uint8_t*>(v.out[0]);
-        A.ids[1] = reinterpret_cast<const uint8_t*>(v.out[1]);
-        A.id_stride = (int)sizeof(rsvio_feature);
-        A.uv[0] = v.undist[0];
-        A.uv[1] = v.undist[1];
-        A.dcount = nullptr;
-        A.n[0] = v.n[0];
-        A.n[1] = v.n[1];
+        const int rc = rsvio::tracker_frame(P, t, A);
+        if (rc != RSVIO_OK) return rc;
         return rsvio::run_pnp(P, A, P.active(), res);
+    });
+}
+
+int rsvio_track_motion_robust(rsvio_pnp* h, const uint64_t* ids_l, const float* uv_l, size_t n_l, const uint64_t* ids_r,
+                              const float* uv_r, size_t n_r, const double* T_W_B_last_kf, const double* T_C_B2,
+                              const rsvio_lm_cfg* cfg, const rsvio_keyframe_rule* rule, const rsvio_ransac_cfg* ransac,
+                              const int32_t* samples, uint8_t* mask_l, uint8_t* mask_r, int32_t* hyp_count,
+                              rsvio_robust_motion_result* res) {
+    if (!h || !T_W_B_last_kf || !T_C_B2 || !cfg || !rule || !res || (n_l && (!ids_l || !uv_l)) ||
+        (n_r && (!ids_r || !uv_r)) || !rsvio::ransac_cfg_ok(ransac))
+        return RSVIO_ERR_INVALID_ARG;
+    if (n_l + n_r > (size_t)rsvio::kPnpMaxFeatures) {
+        rsvio::set_last_error("track_motion: more than 4096 features in one frame");
+        return RSVIO_ERR_CAPACITY;
+    }
+    return guarded([&] {
+        auto& P = h->p;
+        RSVIO_HIP(hipSetDevice(P.device));
+        rsvio::PnpArgs A = rsvio::make_args(P, T_W_B_last_kf, T_C_B2, cfg, rule);
+        rsvio::host_frame(P, ids_l, uv_l, n_l, ids_r, uv_r, n_r, A);
+        return rsvio::run_pnp_robust(P, A, P.active(), ransac, samples, mask_l, mask_r, hyp_count, res);
+    });
+}
+
+int rsvio_track_motion_robust_tracker(rsvio_pnp* h, rsvio_tracker* t, const double* T_W_B_last_kf,
+                                      const double* T_C_B2, const rsvio_lm_cfg* cfg, const rsvio_keyframe_rule* rule,
+                                      const rsvio_ransac_cfg* ransac, const int32_t* samples, uint8_t* mask_l,
+                                      uint8_t* mask_r, int32_t* hyp_count, rsvio_robust_motion_result* res) {
+    if (!h || !t || !T_W_B_last_kf || !T_C_B2 || !cfg || !rule || !res || !rsvio::ransac_cfg_ok(ransac))
+        return RSVIO_ERR_INVALID_ARG;
+    return guarded([&] {
+        auto& P = h->p;
+        rsvio::PnpArgs A = rsvio::make_args(P, T_W_B_last_kf, T_C_B2, cfg, rule);
+        const int rc = rsvio::tracker_frame(P, t, A);
+        if (rc != RSVIO_OK) return rc;
+        return rsvio::run_pnp_robust(P, A, P.active(), ransac, samples, mask_l, mask_r, hyp_count, res);
     });
 }
 

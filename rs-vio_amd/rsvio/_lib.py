@@ -71,6 +71,23 @@ class MotionResult(C.Structure):
                 ("kernel_ms", C.c_double)]
 
 
+class RansacCfg(C.Structure):
+    """rsvio_ransac_cfg (32 B): the hypotheses and the inlier test of rsvio_track_motion_robust."""
+    _fields_ = [("n_hyp", C.c_int32), ("min_inliers", C.c_int32), ("seed", C.c_uint64),
+                ("inlier_sq_error", C.c_double), ("min_depth", C.c_double)]
+
+
+class RobustMotionResult(C.Structure):
+    """rsvio_robust_motion_result (224 B): the refit's motion result and the RANSAC's figures."""
+    _fields_ = [("motion", MotionResult), ("ransac_status", C.c_int32), ("n_pairs", C.c_int32),
+                ("n_valid_pairs", C.c_int32), ("n_valid_hyp", C.c_int32), ("best_hyp", C.c_int32),
+                ("best_count", C.c_int32), ("n_inliers", C.c_int32), ("reserved", C.c_int32),
+                ("device_ms", C.c_double)]
+
+
+RANSAC_STATUS = {1: "Ok", 2: "TooFewPairs", -1: "NoConsensus"}
+
+
 class BaParams(C.Structure):
     _fields_ = [("max_keyframes", C.c_int32), ("max_landmarks", C.c_int32),
                 ("max_observations", C.c_int32), ("device", C.c_int32)]
@@ -147,6 +164,12 @@ SIG = {
                                      C.POINTER(KeyframeRule), C.POINTER(MotionResult)]),
     "rsvio_track_motion_tracker": (C.c_int, [P, P, P, P, C.POINTER(LmCfg), C.POINTER(KeyframeRule),
                                              C.POINTER(MotionResult)]),
+    "rsvio_track_motion_robust": (C.c_int, [P, P, P, C.c_size_t, P, P, C.c_size_t, P, P, C.POINTER(LmCfg),
+                                            C.POINTER(KeyframeRule), C.POINTER(RansacCfg), P, P, P, P,
+                                            C.POINTER(RobustMotionResult)]),
+    "rsvio_track_motion_robust_tracker": (C.c_int, [P, P, P, P, C.POINTER(LmCfg), C.POINTER(KeyframeRule),
+                                                    C.POINTER(RansacCfg), P, P, P, P,
+                                                    C.POINTER(RobustMotionResult)]),
     "rsvio_pyramid_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "rsvio_build_pyramid": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, P]),
     "rsvio_track_points": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, C.c_float,

@@ -102,6 +102,17 @@ class DeviceBackend:
         r = self.motion.track_motion_tracker(self.tracker, T_W_B_last_kf, T_C_B2)
         return r.status, r.is_keyframe, r.T_W_B, r.iterations, r.final_cost
 
+    def track_motion_robust(self, T_W_B_last_kf, T_C_B2, ransac):
+        """track_motion behind the stereo 3-point RANSAC, on the collected frame's device lists;
+        also returns the RobustMotionResult (masks indexed like the collected lists)."""
+        r = self.motion.track_motion_tracker_robust(self.tracker, T_W_B_last_kf, T_C_B2, ransac)
+        m = r.motion
+        return m.status, m.is_keyframe, m.T_W_B, m.iterations, m.final_cost, r
+
+    def remove_ids(self, ids):
+        """StereoPatchTracker::remove_id: the ids leave the tracker before its next frame."""
+        self.tracker.remove_id(np.asarray(ids, np.uint64))
+
     def close(self):
         for o in (self.tracker, self.motion, self.solver, self._ba_stream):
             o.close()
@@ -115,7 +126,22 @@ class Estimator:
     def __init__(self, width: int, height: int, cameras, T_B_Cl, T_B_Cr, levels: int = 6, grid_size: int = 50,
                  max_iterations: int = 20, thresh: float = 0.01, window: int = 10,
                  translation_threshold: float = 0.05, rotation_threshold: float = 0.05, device: int = 0,
-                 backend=None, pipelined: bool = False, landmark_init: str = "ray", gate=None, cull: bool = False):
+                 backend=None, pipelined: bool = False, landmark_init: str = "ray", gate=None, cull: bool = False,
+                 robust_motion=None, drop_outliers: bool = False):
+        # robust_motion: a rsvio.motion.RansacConfig -- the frame's pose and keyframe flag come from
+        # MotionTracker.track_motion_tracker_robust (a stereo 3-point RANSAC, the LM on its
+        # consensus set) instead of the plain LM over every joined observation; None: the
+        # reference's path.  drop_outliers: the ids the robust call marks as outliers leave the
+        # tracker (remove_id) before the next frame is submitted, so run() gives up its look-ahead;
+        # with pipelined the next frame is already being tracked at that point: refused
+        if drop_outliers and pipelined:
+            raise ValueError("drop_outliers needs the tracker idle after motion tracking: not with pipelined=True")
+        if drop_outliers and robust_motion is None:
+            raise ValueError("drop_outliers needs robust_motion (a RansacConfig)")
+        self.robust_motion = robust_motion
+        self.drop_outliers = drop_outliers
+        self.last_robust = None       # the last frame's RobustMotionResult
+        self.last_dropped = np.zeros(0, np.uint64)   # the ids it removed from the tracker
         self.backend = backend or DeviceBackend(width, height, cameras, levels, grid_size, max_iterations, thresh,
                                                 window, translation_threshold, rotation_threshold, device)
         # landmark_init / gate / cull: the window's (SlidingWindow): new landmarks triangulated on the
@@ -163,6 +189,10 @@ class Estimator:
         right after frame t's features are collected, before frame t's motion tracking and BA.
         In pipelined mode a keyframe's FrameResult gets its BA outcome when the solve is next
         waited for (at the latest by flush()); frames left unconsumed are collected on exit."""
+        if self.drop_outliers:  # a frame's outliers leave the tracker before the next one is submitted
+            for left, right in frames:
+                yield self.process_frame(left, right)
+            return
         it = iter(frames)
         nxt = next(it, None)
         if nxt is None:
@@ -194,8 +224,18 @@ class Estimator:
             if self.window.map_version != self._map_key:  # map_points changes only in optimize
                 self.backend.set_map(self.window.map_ids, self.window.map_pw)  # ascending ids, f32
                 self._map_key = self.window.map_version
-            status, is_kf, T_W_B, pnp_iters, pnp_cost = self.backend.track_motion(
-                self.window.keyframes[-1].T_W_B, self._T_C_B2())  # keyframes.back() (sliding_window.rs:506)
+            if self.robust_motion is None:
+                status, is_kf, T_W_B, pnp_iters, pnp_cost = self.backend.track_motion(
+                    self.window.keyframes[-1].T_W_B, self._T_C_B2())  # keyframes.back() (sliding_window.rs:506)
+            else:
+                status, is_kf, T_W_B, pnp_iters, pnp_cost, rob = self.backend.track_motion_robust(
+                    self.window.keyframes[-1].T_W_B, self._T_C_B2(), self.robust_motion)
+                self.last_robust = rob
+                if self.drop_outliers:
+                    out_ids = np.union1d(np.asarray(ids_l)[rob.mask_l == 2], np.asarray(ids_r)[rob.mask_r == 2])
+                    self.last_dropped = out_ids.astype(np.uint64)
+                    if len(out_ids):
+                        self.backend.remove_ids(self.last_dropped)
             pnp_status = status
             if status > 0:
                 frame.T_W_B = T_W_B
@@ -237,7 +277,9 @@ class NativeEstimator:
     between the device calls.  Frame for frame the same outputs as Estimator(pipelined=True).run
     (tests/test_estimator_gpu.py); `stats` holds the host wall time per stage.  The native loop
     keeps the reference's depth-2.0 ray rule for new landmarks: device triangulation and culling
-    (SlidingWindow's landmark_init / cull) are options of the Python Estimator only."""
+    (SlidingWindow's landmark_init / cull) are options of the Python Estimator only, and so is
+    robust motion tracking (Estimator's robust_motion / drop_outliers): the native loop calls the
+    plain rsvio_track_motion_tracker."""
 
     _INT_NONE = -(2 ** 31)
 

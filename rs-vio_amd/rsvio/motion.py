@@ -46,6 +46,57 @@ def _result(r: _lib.MotionResult) -> MotionResult:
                         r.kernel_ms)
 
 
+@dataclass
+class RansacConfig:
+    """rsvio_ransac_cfg: n_hyp hypotheses (h = 0 the prior), the seed of the pair sampler, the
+    inlier test (squared normalised reprojection error: 1e-4 is about 4.6 px at EuRoC's fx; depth
+    along the optical axis: the reference configs' 0.1 m) and the smallest consensus accepted."""
+    n_hyp: int = 256
+    min_inliers: int = 10
+    seed: int = 0
+    inlier_sq_error: float = 1e-4
+    min_depth: float = 0.1
+
+    def to_c(self) -> _lib.RansacCfg:
+        return _lib.RansacCfg(int(self.n_hyp), int(self.min_inliers), int(self.seed) & (2 ** 64 - 1),
+                              float(self.inlier_sq_error), float(self.min_depth))
+
+
+RANSAC_OK, RANSAC_TOO_FEW_PAIRS, RANSAC_NO_CONSENSUS = 1, 2, -1
+
+
+@dataclass
+class RobustMotionResult:
+    """rsvio_robust_motion_result plus the masks (0 no map point, 1 inlier, 2 outlier, indexed like
+    the feature lists) and, on request, the inlier count of every hypothesis (-1: invalid)."""
+    motion: MotionResult
+    ransac_status: int
+    n_pairs: int
+    n_valid_pairs: int
+    n_valid_hyp: int
+    best_hyp: int
+    best_count: int
+    n_inliers: int
+    device_ms: float
+    mask_l: np.ndarray
+    mask_r: np.ndarray
+    hyp_count: np.ndarray | None = None
+
+
+def _samples(samples, n_hyp):
+    if samples is None:
+        return None
+    samples = np.ascontiguousarray(samples, np.int32)
+    if samples.shape != (n_hyp, 3):
+        raise ValueError(f"samples must be n_hyp x 3 = ({n_hyp}, 3), got {samples.shape}")
+    return samples
+
+
+def _robust_result(r: _lib.RobustMotionResult, mask_l, mask_r, counts) -> RobustMotionResult:
+    return RobustMotionResult(_result(r.motion), r.ransac_status, r.n_pairs, r.n_valid_pairs, r.n_valid_hyp,
+                              r.best_hyp, r.best_count, r.n_inliers, r.device_ms, mask_l, mask_r, counts)
+
+
 class MotionTracker:
     """Device handle for track_motion; holds the map (ids ascending, p_W as f32)."""
 
@@ -115,3 +166,45 @@ class MotionTracker:
         check(_lib.load().rsvio_track_motion_tracker(self._h, tracker._h, ptr(Tl), ptr(tcb), C.byref(cfg),
                                                      C.byref(self.rule), C.byref(r)))
         return _result(r)
+
+    def track_motion_robust(self, ids_l, uv_l, ids_r, uv_r, T_W_B_last_kf, T_C_B2, ransac: RansacConfig | None = None,
+                            cfg=None, samples=None, want_counts: bool = False) -> RobustMotionResult:
+        """track_motion behind a stereo 3-point RANSAC (rsvio_track_motion_robust): hypotheses from
+        `samples` (n_hyp x 3 pair indices) or the seeded sampler, the LM on the winner's inliers."""
+        ids_l = np.ascontiguousarray(ids_l, np.uint64).reshape(-1)
+        ids_r = np.ascontiguousarray(ids_r, np.uint64).reshape(-1)
+        uv_l = np.ascontiguousarray(uv_l, np.float32).reshape(-1, 2)
+        uv_r = np.ascontiguousarray(uv_r, np.float32).reshape(-1, 2)
+        Tl = np.ascontiguousarray(T_W_B_last_kf, np.float64).reshape(16)
+        tcb = np.ascontiguousarray(T_C_B2, np.float64).reshape(32)
+        cfg = cfg or pnp_cfg()
+        rc = (ransac or RansacConfig()).to_c()
+        samples = _samples(samples, rc.n_hyp)
+        mask_l, mask_r = np.zeros(len(ids_l), np.uint8), np.zeros(len(ids_r), np.uint8)
+        counts = np.zeros(max(rc.n_hyp, 0), np.int32) if want_counts else None
+        r = _lib.RobustMotionResult()
+        check(_lib.load().rsvio_track_motion_robust(self._h, ptr(ids_l), ptr(uv_l), len(ids_l), ptr(ids_r), ptr(uv_r),
+                                                    len(ids_r), ptr(Tl), ptr(tcb), C.byref(cfg), C.byref(self.rule),
+                                                    C.byref(rc), ptr(samples), ptr(mask_l), ptr(mask_r), ptr(counts),
+                                                    C.byref(r)))
+        return _robust_result(r, mask_l, mask_r, counts)
+
+    def track_motion_tracker_robust(self, tracker, T_W_B_last_kf, T_C_B2, ransac: RansacConfig | None = None,
+                                    cfg=None, samples=None, want_counts: bool = False) -> RobustMotionResult:
+        """The robust call on the tracker's last collected frame, read on the device; the masks
+        are indexed like the collected feature lists."""
+        Tl = np.ascontiguousarray(T_W_B_last_kf, np.float64).reshape(16)
+        tcb = np.ascontiguousarray(T_C_B2, np.float64).reshape(32)
+        cfg = cfg or pnp_cfg()
+        rc = (ransac or RansacConfig()).to_c()
+        samples = _samples(samples, rc.n_hyp)
+        # the library writes as many bytes as the collected frame has features: buffers of the
+        # tracker's capacity, cut to the collected lists' lengths
+        n_l, n_r = tracker._n
+        mask_l, mask_r = np.zeros(max(tracker.cap, n_l), np.uint8), np.zeros(max(tracker.cap, n_r), np.uint8)
+        counts = np.zeros(max(rc.n_hyp, 0), np.int32) if want_counts else None
+        r = _lib.RobustMotionResult()
+        check(_lib.load().rsvio_track_motion_robust_tracker(self._h, tracker._h, ptr(Tl), ptr(tcb), C.byref(cfg),
+                                                            C.byref(self.rule), C.byref(rc), ptr(samples),
+                                                            ptr(mask_l), ptr(mask_r), ptr(counts), C.byref(r)))
+        return _robust_result(r, mask_l[:n_l].copy(), mask_r[:n_r].copy(), counts)
