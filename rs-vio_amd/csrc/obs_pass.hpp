@@ -5,8 +5,11 @@
 // window goes up, set_problem turns them into packed keys l << 6 | k << 1 | c, one (keyframe,
 // camera) bit mask per landmark, and the (u, v) narrowed to f32 when that is exact -- a pass over
 // ~25 B in and ~12 B out per observation (24,000 observations at config 3: ~0.9 MB), bound by one
-// core's cache bandwidth.  On the headline step it sits on the critical path before the solve can
-// start, so it is cut into landmark-run-aligned chunks that the calling thread and a few helper
+// core's cache bandwidth.  Keys and masks come out of one vectorised sweep (keys_masks: the bits of
+// 8 keys formed in registers, one mask store per landmark run), the (u, v) out of a second one
+// (uv_narrow); the code path is chosen at run time (simd_level), with the scalar loops as the
+// fallback.  On the headline step the pass sits on the critical path before the solve can
+// start, so it can be cut into landmark-run-aligned chunks that the calling thread and a few helper
 // threads take by a CAS on one word (HostPool): a helper that is parked or descheduled only leaves
 // its chunks to the others, so the pass is never slower than the caller alone by more than one
 // futex wake.  Every chunk writes disjoint keys, (u, v) and -- its runs being whole -- disjoint
@@ -29,6 +32,33 @@
 
 namespace rsvio_obs {
 
+// (tools/obs_pass_phases.cpp times the fused sweep when the header has one)
+#define RSVIO_OBS_FUSED 1
+
+// ---- the code path of every sub-pass, chosen once at run time (the library is built without
+// -march and loads on any x86-64 host): kScalar, kAvx2 or kAvx512 (AVX-512F on top of AVX2), the best the
+// host has unless RSVIO_OBS_SIMD=scalar|avx2|avx512 asks for less.  simd_level() is a reference so
+// that tools/obs_pass_equiv.cpp can run every level against its reference loop.
+enum { kScalar = 0, kAvx2 = 1, kAvx512 = 2 };
+static int simd_host_level() {
+    if (!__builtin_cpu_supports("avx2") || !__builtin_cpu_supports("popcnt")) return kScalar;
+    return __builtin_cpu_supports("avx512f") ? kAvx512 : kAvx2;
+}
+static int& simd_level() {
+    static int level = [] {
+        int lv = simd_host_level();
+        if (const char* e = std::getenv("RSVIO_OBS_SIMD")) {
+            if (!std::strcmp(e, "scalar")) lv = kScalar;
+            if (!std::strcmp(e, "avx2")) lv = std::min(lv, (int)kAvx2);
+        }
+        return lv;
+    }();
+    return level;
+}
+
+#define RSVIO_T_AVX2 __attribute__((target("avx2,popcnt")))
+#define RSVIO_T_AVX512 __attribute__((target("avx512f,avx2")))
+
 // ---- the (u, v) as f32 when every value is exactly an f32 (the estimator's are: normalised
 // coordinates unprojected from f32 pixels and stored as f32 features, frame.rs:107-134 ->
 // sliding_window.rs:274-300), halving the largest part of the window's PCIe upload; false (nothing
@@ -49,9 +79,26 @@ __attribute__((target("avx2"))) static bool uv_narrow_avx2(size_t n2, const doub
     }
     return ok;
 }
+RSVIO_T_AVX512 static bool uv_narrow_avx512(size_t n2, const double* uv, float* out) {
+    size_t i = 0;
+    __mmask8 bad = 0;
+    for (; i + 8 <= n2; i += 8) {
+        const __m512d d = _mm512_loadu_pd(uv + i);
+        const __m256 f = _mm512_cvtpd_ps(d);
+        bad |= _mm512_cmp_pd_mask(_mm512_cvtps_pd(f), d, _CMP_NEQ_UQ);
+        _mm256_storeu_ps(out + i, f);
+    }
+    bool ok = bad == 0;
+    for (; i < n2; ++i) {
+        out[i] = (float)uv[i];
+        ok &= (double)out[i] == uv[i];
+    }
+    return ok;
+}
 static bool uv_narrow(size_t n2, const double* uv, float* out) {
-    static const bool avx2 = __builtin_cpu_supports("avx2");
-    if (avx2) return uv_narrow_avx2(n2, uv, out);
+    const int lv = simd_level();
+    if (lv >= kAvx512) return uv_narrow_avx512(n2, uv, out);
+    if (lv >= kAvx2) return uv_narrow_avx2(n2, uv, out);
     bool ok = true;
     for (size_t i = 0; i < n2; ++i) {
         out[i] = (float)uv[i];
@@ -90,8 +137,7 @@ __attribute__((target("avx2"))) static bool obs_keys_avx2(int n_obs, const int32
 static bool obs_keys(int n_obs, const int32_t* lm, const int32_t* kf, const uint8_t* cam, int n_lm, int n_kf,
                      unsigned* key) {
     if (n_lm <= 0 || n_kf <= 0) return false;
-    static const bool avx2 = __builtin_cpu_supports("avx2");
-    if (avx2) return obs_keys_avx2(n_obs, lm, kf, cam, n_lm, n_kf, key);
+    if (simd_level() >= kAvx2) return obs_keys_avx2(n_obs, lm, kf, cam, n_lm, n_kf, key);
     unsigned bad = 0;
     for (int i = 0; i < n_obs; ++i) {
         const unsigned l = (unsigned)lm[i], k = (unsigned)kf[i], c = cam[i];
@@ -153,6 +199,140 @@ static bool obs_masks_runs(int n_obs, const unsigned* key, int n_lm, unsigned lo
     std::memset(m2, 0, sizeof(unsigned long long) * (size_t)n_lm);
     masks_of_runs(0, n_obs, key, m2);
     return mask_bits(n_lm, m2) == n_obs;
+}
+
+// ======================================================================================
+// The fused sweep: keys (+ validation) and run masks of the observations [a, b) in one pass over
+// obs_lm / obs_kf / obs_cam, 8 observations per step.  The group's 8 bits 1 << (k << 1 | c) are
+// formed from the keys while those are still in registers (vpsllvq) and ORed into a *vector*
+// accumulator of the current run; a run start (lm[i] != lm[i - 1], one compare of the group against
+// itself loaded one observation earlier) reduces the accumulator to one word and stores it to the
+// finished run's landmark -- one store per run, not per observation, and no load of m2 at all.
+// What the scalar chains guarantee is kept as it is: a run's mask is *stored*, never ORed into m2,
+// so a landmark in two runs keeps only its last run's bits and a duplicate keeps one bit for two
+// observations, and either way the total bit count falls short of n_obs (the caller's check; [a, b)
+// must start at a run start, as every chunk does).  An index out of range returns false before
+// anything of its group is stored, so m2 is never indexed by one.  n_kf <= 32 (a bit per (k, c)).
+
+// the observations [i, b) one at a time, continuing the run whose mask so far is cm and whose
+// landmark's entry is slot (the vector sweeps' tail, and all of a short list)
+static bool keys_masks_tail(int a, int i, int b, const int32_t* lm, const int32_t* kf, const uint8_t* cam,
+                            int n_lm, int n_kf, unsigned* key, unsigned long long* m2, unsigned long long cm,
+                            unsigned long long* slot) {
+    for (; i < b; ++i) {
+        const unsigned l = (unsigned)lm[i], k = (unsigned)kf[i], c = cam[i];
+        if ((l >= (unsigned)n_lm) | (k >= (unsigned)n_kf) | (c > 1)) return false;
+        key[i] = l << 6 | k << 1 | c;
+        const unsigned long long bit = 1ull << (k << 1 | c);
+        if (i == a || lm[i] != lm[i - 1]) {
+            // (relaxed atomic: two chunks store the same landmark only when its observations are
+            // not one run, which the bit count rejects)
+            __atomic_store_n(slot, cm, __ATOMIC_RELAXED);
+            slot = m2 + l;
+            cm = bit;
+        } else {
+            cm |= bit;
+        }
+    }
+    __atomic_store_n(slot, cm, __ATOMIC_RELAXED);
+    return true;
+}
+
+RSVIO_T_AVX2 static inline unsigned long long or_lanes_avx2(__m256i v) {
+    const __m128i x = _mm_or_si128(_mm256_castsi256_si128(v), _mm256_extracti128_si256(v, 1));
+    return (unsigned long long)_mm_cvtsi128_si64(x) | (unsigned long long)_mm_extract_epi64(x, 1);
+}
+
+// half a group: the bits v of the observations lm4[0 .. 4) and their run starts st (bit j:
+// observation j starts a run).  No start: one OR.  One start (every run of 4 or more): the lanes
+// before it finish the current run, the others begin the next.  More: the lanes one at a time.
+RSVIO_T_AVX2 static inline void half_group_avx2(__m256i v, unsigned st, const int32_t* lm4, unsigned long long* m2,
+                                                __m256i& cmv, unsigned long long*& slot) {
+    alignas(32) static const unsigned long long kLanes[8] = {~0ull, ~0ull, ~0ull, ~0ull, 0, 0, 0, 0};
+    if (!st) {
+        cmv = _mm256_or_si256(cmv, v);
+        return;
+    }
+    const int p = __builtin_ctz(st);
+    const __m256i before = _mm256_loadu_si256(reinterpret_cast<const __m256i*>(kLanes + 4 - p));  // lanes < p
+    cmv = _mm256_or_si256(cmv, _mm256_and_si256(v, before));
+    __atomic_store_n(slot, or_lanes_avx2(cmv), __ATOMIC_RELAXED);
+    slot = m2 + lm4[p];
+    if (!(st >> (p + 1))) {
+        cmv = _mm256_andnot_si256(before, v);
+        return;
+    }
+    alignas(32) unsigned long long bv[4];
+    _mm256_store_si256(reinterpret_cast<__m256i*>(bv), v);
+    unsigned long long cm = bv[p];
+    for (int j = p + 1; j < 4; ++j) {
+        if (st >> j & 1) {
+            __atomic_store_n(slot, cm, __ATOMIC_RELAXED);
+            slot = m2 + lm4[j];
+            cm = bv[j];
+        } else {
+            cm |= bv[j];
+        }
+    }
+    cmv = _mm256_set_epi64x(0, 0, 0, (long long)cm);
+}
+
+RSVIO_T_AVX2 static bool keys_masks_avx2(int a, int b, const int32_t* lm, const int32_t* kf, const uint8_t* cam,
+                                         int n_lm, int n_kf, unsigned* key, unsigned long long* m2) {
+    const __m256i nl1 = _mm256_set1_epi32(n_lm - 1), nk1 = _mm256_set1_epi32(n_kf - 1), one = _mm256_set1_epi32(1);
+    const __m256i c63 = _mm256_set1_epi32(63), one64 = _mm256_set1_epi64x(1);
+    const __m256i back1 = _mm256_setr_epi32(0, 0, 1, 2, 3, 4, 5, 6);
+    unsigned long long sink = 0, *slot = &sink;  // (the "run" before the first one)
+    __m256i cmv = _mm256_setzero_si256();
+    int i = a;
+    for (; i + 8 <= b; i += 8) {
+        const __m256i l = _mm256_loadu_si256(reinterpret_cast<const __m256i*>(lm + i));
+        const __m256i k = _mm256_loadu_si256(reinterpret_cast<const __m256i*>(kf + i));
+        const __m256i c = _mm256_cvtepu8_epi32(_mm_loadl_epi64(reinterpret_cast<const __m128i*>(cam + i)));
+        // x > n - 1 (unsigned; negative indices are huge)  <=>  max(x, n - 1) != n - 1
+        const __m256i bad = _mm256_or_si256(
+            _mm256_or_si256(_mm256_xor_si256(_mm256_max_epu32(l, nl1), nl1), _mm256_xor_si256(_mm256_max_epu32(k, nk1), nk1)),
+            _mm256_xor_si256(_mm256_max_epu32(c, one), one));
+        if (!_mm256_testz_si256(bad, bad)) return false;
+        const __m256i kk = _mm256_or_si256(_mm256_or_si256(_mm256_slli_epi32(l, 6), _mm256_slli_epi32(k, 1)), c);
+        _mm256_storeu_si256(reinterpret_cast<__m256i*>(key + i), kk);
+        // run starts: lm[i + j] != lm[i + j - 1]; the first observation of [a, b) starts one
+        unsigned st;
+        if (i == a) {
+            st = ~(unsigned)_mm256_movemask_ps(_mm256_castsi256_ps(
+                     _mm256_cmpeq_epi32(l, _mm256_permutevar8x32_epi32(l, back1)))) & 0xffu;
+            st |= 1u;
+        } else {
+            const __m256i prev = _mm256_loadu_si256(reinterpret_cast<const __m256i*>(lm + i - 1));
+            st = ~(unsigned)_mm256_movemask_ps(_mm256_castsi256_ps(_mm256_cmpeq_epi32(l, prev))) & 0xffu;
+        }
+        const __m256i sh = _mm256_and_si256(kk, c63);
+        const __m256i v0 = _mm256_sllv_epi64(one64, _mm256_cvtepu32_epi64(_mm256_castsi256_si128(sh)));
+        const __m256i v1 = _mm256_sllv_epi64(one64, _mm256_cvtepu32_epi64(_mm256_extracti128_si256(sh, 1)));
+        if (!st) {
+            cmv = _mm256_or_si256(cmv, _mm256_or_si256(v0, v1));
+        } else {
+            half_group_avx2(v0, st & 15u, lm + i, m2, cmv, slot);
+            half_group_avx2(v1, st >> 4, lm + i + 4, m2, cmv, slot);
+        }
+    }
+    return keys_masks_tail(a, i, b, lm, kf, cam, n_lm, n_kf, key, m2, or_lanes_avx2(cmv), slot);
+}
+
+// (The same sweep with 512-bit registers -- the 8 bits of a group in one register, the run starts
+// in a mask register -- measured no faster: 5.5 vs 5.2 us at config 3 and 17.1 vs 15.3 us at config
+// 5 on an EPYC 9575F, profiles/r09_obs_pass_phases.txt; so kAvx512 only changes uv_narrow.)
+
+// keys and run masks of [a, b) by the host's best path; false if an index is out of range.  m2 is
+// zeroed by the caller, who also checks the total bit count.
+static bool keys_masks(int a, int b, const int32_t* lm, const int32_t* kf, const uint8_t* cam, int n_lm, int n_kf,
+                       unsigned* key, unsigned long long* m2) {
+    if (n_lm <= 0 || n_kf <= 0) return false;
+    const int lv = n_kf <= 32 ? simd_level() : (int)kScalar;
+    if (lv >= kAvx2) return keys_masks_avx2(a, b, lm, kf, cam, n_lm, n_kf, key, m2);
+    if (!obs_keys(b - a, lm + a, kf + a, cam + a, n_lm, n_kf, key + a)) return false;
+    masks_of_runs(a, b, key, m2);
+    return true;
 }
 
 // ======================================================================================
@@ -278,10 +458,8 @@ struct ObsJob {
     static void chunk(void* p, int c) {
         ObsJob& J = *static_cast<ObsJob*>(p);
         const int a = J.cut[c], b = J.cut[c + 1];
-        if (!obs_keys(b - a, J.lm + a, J.kf + a, J.cam + a, J.n_lm, J.n_kf, J.key + a))
+        if (!keys_masks(a, b, J.lm, J.kf, J.cam, J.n_lm, J.n_kf, J.key, J.m2))
             J.bad.store(1, std::memory_order_relaxed);
-        else
-            masks_of_runs(a, b, J.key, J.m2);
         if (J.uv32 && !uv_narrow(2 * (size_t)(b - a), J.uv + 2 * (size_t)a, J.uv32 + 2 * (size_t)a))
             J.wide.store(1, std::memory_order_relaxed);
     }
@@ -343,8 +521,7 @@ static bool observation_pass(int n_obs, const int32_t* lm, const int32_t* kf, co
         }
     }
     *narrowed = uv32 && uv_narrow(2 * (size_t)n_obs, uv, uv32);
-    if (!obs_keys(n_obs, lm, kf, cam, n_lm, n_kf, key)) return false;
-    masks_of_runs(0, n_obs, key, m2);
+    if (!keys_masks(0, n_obs, lm, kf, cam, n_lm, n_kf, key, m2)) return false;
     return mask_bits(n_lm, m2) == n_obs;
 }
 
