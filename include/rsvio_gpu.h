@@ -639,6 +639,51 @@ int rsvio_track_motion_robust_tracker(rsvio_pnp* p, rsvio_tracker* t, const doub
                                       const int32_t* samples, uint8_t* mask_l, uint8_t* mask_r,
                                       int32_t* hyp_count, rsvio_robust_motion_result* res);
 
+/* Batched motion tracking (the serving mode's third leg beside rsvio_track_points_table_d and
+ * rsvio_ba_batch_*): n handles, each with its own map, and ONE frame per handle tracked by one
+ * launch (plain; workgroup i is stream i) or three (robust: join on a grid of n, score on
+ * (n_hyp, n), refit on n) with one upload and one host wait.  results[i] is exactly -- bit for
+ * bit, keyframe rule included -- what rsvio_track_motion / rsvio_track_motion_robust returns for
+ * frame i on handle i; kernel_ms is that workgroup's own device time, *device_ms (may be NULL)
+ * and, on the robust path, every results[i].device_ms the whole batch's launches by HIP events.
+ * A frame whose LM fails or is skipped is a normal result.
+ *   The batch borrows the handles (they must outlive it; all on one device; the same handle may
+ * sit in several slots) and runs on a stream of its own.  Every run reads each handle's CURRENT
+ * map, so an rsvio_pnp_set_map between two runs is picked up; the map is read-only during a run.
+ *   A frame's lists are host arrays (on_device = 0: staged into the batch's one upload) or DEVICE
+ * pointers read in place (on_device = 1: ids `id_stride` bytes apart, 0 meaning 8 -- e.g.
+ * sizeof(rsvio_feature) for the tracker's output -- and uv as float pairs), complete on the
+ * device before the call.  frames[i].cfg overrides the call's cfg for slot i; `samples`, `mask_l`,
+ * `mask_r` and `hyp_count` are as in rsvio_track_motion_robust (ignored by the plain call).
+ *   Everything is checked before anything is launched or written: 1 <= n <= 4096; a NULL
+ * argument, a bad `ransac`, an id_stride in 1..7 or no cfg at all for a frame is
+ * RSVIO_ERR_INVALID_ARG; a frame with n_l + n_r > 4096 is RSVIO_ERR_CAPACITY and
+ * rsvio_last_error names the slot.  The kernels hold a frame's features in LDS entries for 1024
+ * features when the batch's largest frame has at most 1024 (several workgroups per CU), for 4096
+ * otherwise; RSVIO_PNP_BATCH_CAP=4096 in the environment forces the large form.  The choice
+ * changes no bit of any result. */
+typedef struct rsvio_pnp_batch rsvio_pnp_batch;
+typedef struct {
+    const uint64_t* ids_l;  const float* uv_l;  size_t n_l;   /* as rsvio_track_motion */
+    const uint64_t* ids_r;  const float* uv_r;  size_t n_r;
+    const double* T_W_B_last_kf;   /* 16 */
+    const double* T_C_B2;          /* 32 */
+    const rsvio_lm_cfg* cfg;       /* NULL: the call's cfg */
+    const int32_t* samples;        /* robust only: n_hyp x 3, or NULL: the seeded sampler */
+    uint8_t* mask_l; uint8_t* mask_r; int32_t* hyp_count;  /* robust only; each may be NULL */
+    int32_t on_device;   /* 0: ids/uv are host arrays.  1: DEVICE pointers, read in place */
+    int32_t id_stride;   /* bytes between ids (0 means 8); e.g. sizeof(rsvio_feature) for tracker output */
+} rsvio_motion_frame;
+int rsvio_pnp_batch_create(rsvio_pnp* const* handles, int32_t n, rsvio_pnp_batch** out);
+int rsvio_pnp_batch_track_motion(rsvio_pnp_batch* b, const rsvio_motion_frame* frames,
+                                 const rsvio_lm_cfg* cfg, const rsvio_keyframe_rule* rule,
+                                 rsvio_motion_result* results, double* device_ms);
+int rsvio_pnp_batch_track_motion_robust(rsvio_pnp_batch* b, const rsvio_motion_frame* frames,
+                                        const rsvio_lm_cfg* cfg, const rsvio_keyframe_rule* rule,
+                                        const rsvio_ransac_cfg* ransac,
+                                        rsvio_robust_motion_result* results, double* device_ms);
+void rsvio_pnp_batch_destroy(rsvio_pnp_batch* b);
+
 #ifdef __cplusplus
 }
 #endif

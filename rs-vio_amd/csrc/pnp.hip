@@ -28,6 +28,8 @@
 // the first is at a trial pose: if the step is accepted its H and g are the next system, so an
 // accepted iteration costs one pass.
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <algorithm>
 #include <stdexcept>
@@ -458,10 +460,15 @@ __device__ __forceinline__ bool map_lookup(const PnpArgs& A, uint64_t id, float 
     return false;
 }
 
-__global__ __launch_bounds__(kPnpThreads) void pnp_track_motion_kernel(PnpArgs A) {
-    __shared__ float s_mpw[3][kPnpMaxFeatures];  // the matched map point per feature
-    __shared__ float s_uv[2][kPnpMaxFeatures];   // undistorted coordinates per feature
-    __shared__ int8_t s_cam[kPnpMaxFeatures];    // feature -> camera, -1: no map point
+// The whole of track_motion for one frame, run by one workgroup of kPnpThreads lanes: the body of
+// pnp_track_motion_kernel (A by value, in the kernel arguments) and of
+// pnp_track_motion_batch_kernel (A in a device table, one entry per workgroup).  CAP: the LDS
+// entries for features (feature j at entry j whatever CAP is, so CAP changes no result).
+template <int CAP>
+__device__ __forceinline__ void pnp_track_motion_body(const PnpArgs& A) {
+    __shared__ float s_mpw[3][CAP];              // the matched map point per feature
+    __shared__ float s_uv[2][CAP];               // undistorted coordinates per feature
+    __shared__ int8_t s_cam[CAP];                // feature -> camera, -1: no map point
     __shared__ double s_red[kPnpWaves][kRed];
     __shared__ double s_sum[kRed];
     __shared__ double s_pose[12];                // R_BW, t_BW of the pass pose (wave 0's)
@@ -476,7 +483,7 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_track_motion_kernel(PnpArgs A
     const int n0 = A.dcount ? A.dcount[0] : A.n[0];
     const int n1 = A.dcount ? A.dcount[1] : A.n[1];
     const int nf = n0 + n1;
-    const bool fits = nf <= kPnpMaxFeatures;
+    const bool fits = nf <= CAP;
     // the factor list: features with a map point, left then right (sliding_window.rs:519-547);
     // feature j's observation goes to LDS entry j (cam -1: no map point).  Two features per lane
     // per round: both id / uv loads, then both bucket loads in flight together.
@@ -642,6 +649,17 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_track_motion_kernel(PnpArgs A
     STAMP(28);
     if (tid == 0) pnp_finish(A, s_ctl, t_entry);
     STAMP(29);
+}
+
+__global__ __launch_bounds__(kPnpThreads) void pnp_track_motion_kernel(PnpArgs A) {
+    pnp_track_motion_body<kPnpMaxFeatures>(A);
+}
+
+// Batched: workgroup blockIdx.x is stream i, its arguments entry i of a table in device memory
+// (uniform over the workgroup: scalar loads).  No workgroup reads what another writes.
+template <int CAP>
+__global__ __launch_bounds__(kPnpThreads) void pnp_track_motion_batch_kernel(const PnpArgs* __restrict__ table) {
+    pnp_track_motion_body<CAP>(table[blockIdx.x]);
 }
 
 #include "pnp_robust.hpp"
@@ -896,10 +914,283 @@ int run_pnp_robust(Pnp& p, PnpArgs A, hipStream_t stream, const rsvio_ransac_cfg
     return RSVIO_OK;
 }
 
+// ---- batched motion tracking: one frame per handle, all in one launch chain ----
+
+constexpr int kPnpBatchMax = 4096;       // handles per batch
+constexpr int kPnpBatchSmallCap = 1024;  // the batched kernels' small LDS capacity (features)
+
+inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+struct PnpBatch {
+    int device = 0, n = 0;
+    std::vector<Pnp*> h;               // borrowed
+    hipStream_t stream = nullptr;      // the batch's own
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    // one image per call: the argument table, then every host frame's [ids_l | ids_r | uv_l | uv_r]
+    // and (robust) the explicit samples, each at a 16-byte-aligned offset; one H2D copy moves it
+    HostBuf<uint8_t> himg;
+    DevBuf<uint8_t> dimg;
+    std::vector<size_t> frame_off, samp_off;
+    HostBuf<rsvio_motion_result> hres;             // the kernels' result table (plain)
+    HostBuf<rsvio_robust_motion_result> hrobust;   // ... (robust)
+    // the robust path's per-stream scratch (RobustBufs), allocated by the first robust run
+    DevBuf<double> rdbl;
+    DevBuf<int> rint;
+    DevBuf<int> rcount;                // hyp_count: stream i at i * n_hyp
+    DevBuf<uint8_t> rmask;             // mask: stream i at i * (the call's mask stride)
+    HostBuf<int> hcount;
+    HostBuf<uint8_t> hmask;
+    double device_ms = 0.0;
+
+    static constexpr size_t kDblPerStream = 11 * (size_t)kPnpMaxFeatures + 12 * (size_t)kRansacMaxHyp;
+    static constexpr size_t kIntPerStream = 3 * (size_t)kPnpMaxFeatures + 4;
+
+    void init(int dev, std::vector<Pnp*> handles) {
+        device = dev;
+        h = std::move(handles);
+        n = (int)h.size();
+        frame_off.resize(n);
+        samp_off.resize(n);
+        RSVIO_HIP(hipSetDevice(dev));
+        RSVIO_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        RSVIO_HIP(hipEventCreate(&ev[0]));
+        RSVIO_HIP(hipEventCreate(&ev[1]));
+        hres.alloc(n);
+    }
+    void init_robust() {
+        if (hrobust.p) return;
+        rdbl.alloc(kDblPerStream * n);
+        rint.alloc(kIntPerStream * n);
+        rcount.alloc((size_t)kRansacMaxHyp * n);
+        rmask.alloc((size_t)kPnpMaxFeatures * n);
+        hrobust.alloc(n);
+    }
+    void reserve_image(size_t bytes) {  // (no copy is in flight: every run ends with a host wait)
+        if (himg.n >= bytes) return;
+        const size_t cap = bytes + bytes / 2;
+        himg.alloc(cap);
+        dimg.alloc(cap);
+    }
+    ~PnpBatch() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+// The host-side checks of a batched call: nothing is launched or written unless all pass
+int batch_check(const PnpBatch& b, const rsvio_motion_frame* frames, const rsvio_lm_cfg* cfg, const char* who) {
+    for (int i = 0; i < b.n; ++i) {
+        const rsvio_motion_frame& f = frames[i];
+        if (!f.T_W_B_last_kf || !f.T_C_B2 || (!f.cfg && !cfg) || (f.n_l && (!f.ids_l || !f.uv_l)) ||
+            (f.n_r && (!f.ids_r || !f.uv_r)) || f.id_stride < 0 || (f.id_stride && f.id_stride < 8)) {
+            char msg[96];
+            std::snprintf(msg, sizeof msg, "%s: slot %d: a NULL argument, no cfg or a bad id_stride", who, i);
+            set_last_error(msg);
+            return RSVIO_ERR_INVALID_ARG;
+        }
+    }
+    for (int i = 0; i < b.n; ++i)
+        if (frames[i].n_l > (size_t)kPnpMaxFeatures || frames[i].n_r > (size_t)kPnpMaxFeatures ||
+            frames[i].n_l + frames[i].n_r > (size_t)kPnpMaxFeatures) {
+            char msg[96];
+            std::snprintf(msg, sizeof msg, "%s: slot %d: more than 4096 features in one frame", who, i);
+            set_last_error(msg);
+            return RSVIO_ERR_CAPACITY;
+        }
+    return RSVIO_OK;
+}
+
+// The LDS capacity of this call's kernels: the small one when the batch's largest frame fits
+// (several workgroups per CU), RSVIO_PNP_BATCH_CAP=4096 forcing the large one
+int batch_cap(const PnpBatch& b, const rsvio_motion_frame* frames) {
+    size_t most = 0;
+    for (int i = 0; i < b.n; ++i) most = std::max(most, frames[i].n_l + frames[i].n_r);
+    const char* e = std::getenv("RSVIO_PNP_BATCH_CAP");
+    if (e && std::atoi(e) == kPnpMaxFeatures) return kPnpMaxFeatures;
+    return most <= (size_t)kPnpBatchSmallCap ? kPnpBatchSmallCap : kPnpMaxFeatures;
+}
+
+// Lay the call's image out (table of n entries of `entry` bytes, host frames, samples of
+// `samp_bytes` each where given) and stage the host frames and samples; returns its size
+size_t batch_stage(PnpBatch& b, const rsvio_motion_frame* frames, size_t entry, size_t samp_bytes) {
+    size_t off = align16(entry * (size_t)b.n);
+    for (int i = 0; i < b.n; ++i) {
+        const rsvio_motion_frame& f = frames[i];
+        b.frame_off[i] = off;
+        if (!f.on_device) off += 16 * (f.n_l + f.n_r);
+        b.samp_off[i] = off;
+        if (samp_bytes && f.samples) off += align16(samp_bytes);
+    }
+    b.reserve_image(off);
+    for (int i = 0; i < b.n; ++i) {
+        const rsvio_motion_frame& f = frames[i];
+        if (!f.on_device) {
+            uint8_t* hb = b.himg.p + b.frame_off[i];
+            const size_t n = f.n_l + f.n_r;
+            if (f.n_l) std::memcpy(hb, f.ids_l, 8 * f.n_l);
+            if (f.n_r) std::memcpy(hb + 8 * f.n_l, f.ids_r, 8 * f.n_r);
+            if (f.n_l) std::memcpy(hb + 8 * n, f.uv_l, 8 * f.n_l);
+            if (f.n_r) std::memcpy(hb + 8 * n + 8 * f.n_l, f.uv_r, 8 * f.n_r);
+        }
+        if (samp_bytes && f.samples) std::memcpy(b.himg.p + b.samp_off[i], f.samples, samp_bytes);
+    }
+    return off;
+}
+
+// Slot i's PnpArgs: handle i's current map, frame i's poses, cfg and lists
+PnpArgs batch_args(PnpBatch& b, int i, const rsvio_motion_frame& f, const rsvio_lm_cfg* cfg,
+                   const rsvio_keyframe_rule* rule) {
+    PnpArgs A = make_args(*b.h[i], f.T_W_B_last_kf, f.T_C_B2, f.cfg ? f.cfg : cfg, rule);
+    if (f.on_device) {  // device pointers, read in place
+        A.ids[0] = reinterpret_cast<const uint8_t*>(f.ids_l);
+        A.ids[1] = reinterpret_cast<const uint8_t*>(f.ids_r);
+        A.id_stride = f.id_stride ? f.id_stride : 8;
+        A.uv[0] = reinterpret_cast<const float2*>(f.uv_l);
+        A.uv[1] = reinterpret_cast<const float2*>(f.uv_r);
+    } else {
+        const uint8_t* d = b.dimg.p + b.frame_off[i];
+        const size_t n = f.n_l + f.n_r;
+        A.ids[0] = d;
+        A.ids[1] = d + 8 * f.n_l;
+        A.id_stride = 8;
+        A.uv[0] = reinterpret_cast<const float2*>(d + 8 * n);
+        A.uv[1] = reinterpret_cast<const float2*>(d + 8 * n + 8 * f.n_l);
+    }
+    A.dcount = nullptr;
+    A.n[0] = (int)f.n_l;
+    A.n[1] = (int)f.n_r;
+    return A;
+}
+
+int run_pnp_batch(PnpBatch& b, const rsvio_motion_frame* frames, const rsvio_lm_cfg* cfg,
+                  const rsvio_keyframe_rule* rule, rsvio_motion_result* results, double* device_ms) {
+    RSVIO_HIP(hipSetDevice(b.device));
+    const int cap = batch_cap(b, frames);
+    const size_t bytes = batch_stage(b, frames, sizeof(PnpArgs), 0);
+    PnpArgs* tab = reinterpret_cast<PnpArgs*>(b.himg.p);
+    for (int i = 0; i < b.n; ++i) {
+        tab[i] = batch_args(b, i, frames[i], cfg, rule);
+        tab[i].out = b.hres.p + i;
+    }
+    RSVIO_HIP(hipMemcpyAsync(b.dimg.p, b.himg.p, bytes, hipMemcpyHostToDevice, b.stream));
+    const PnpArgs* dtab = reinterpret_cast<const PnpArgs*>(b.dimg.p);
+    RSVIO_HIP(hipEventRecord(b.ev[0], b.stream));
+    if (cap == kPnpBatchSmallCap)
+        hipLaunchKernelGGL(pnp_track_motion_batch_kernel<kPnpBatchSmallCap>, dim3(b.n), dim3(kPnpThreads), 0,
+                           b.stream, dtab);
+    else
+        hipLaunchKernelGGL(pnp_track_motion_batch_kernel<kPnpMaxFeatures>, dim3(b.n), dim3(kPnpThreads), 0, b.stream,
+                           dtab);
+    RSVIO_HIP(hipGetLastError());
+    RSVIO_HIP(hipEventRecord(b.ev[1], b.stream));
+    RSVIO_HIP(hipStreamSynchronize(b.stream));
+    float ms = 0.f;
+    RSVIO_HIP(hipEventElapsedTime(&ms, b.ev[0], b.ev[1]));
+    b.device_ms = ms;
+    if (device_ms) *device_ms = ms;
+    for (int i = 0; i < b.n; ++i) {
+        results[i] = b.hres.p[i];
+        keyframe_rule(tab[i], &results[i]);
+    }
+    return RSVIO_OK;
+}
+
+int run_pnp_batch_robust(PnpBatch& b, const rsvio_motion_frame* frames, const rsvio_lm_cfg* cfg,
+                         const rsvio_keyframe_rule* rule, const rsvio_ransac_cfg* rc,
+                         rsvio_robust_motion_result* results, double* device_ms) {
+    RSVIO_HIP(hipSetDevice(b.device));
+    b.init_robust();
+    constexpr size_t fcap = kPnpMaxFeatures;
+    const int cap = batch_cap(b, frames);
+    const size_t n_hyp = (size_t)rc->n_hyp;
+    const size_t bytes = batch_stage(b, frames, sizeof(RobustArgs), sizeof(int32_t) * 3 * n_hyp);
+    size_t most = 0;
+    bool want_mask = false, want_count = false;
+    for (int i = 0; i < b.n; ++i) {
+        most = std::max(most, frames[i].n_l + frames[i].n_r);
+        want_mask |= frames[i].mask_l || frames[i].mask_r;
+        want_count |= frames[i].hyp_count != nullptr;
+    }
+    const size_t mstride = align16(most);
+    RobustArgs* tab = reinterpret_cast<RobustArgs*>(b.himg.p);
+    for (int i = 0; i < b.n; ++i) {
+        RobustArgs RA{};
+        RA.P = batch_args(b, i, frames[i], cfg, rule);
+        RA.P.out = &b.hrobust.p[i].motion;
+        double* d = b.rdbl.p + PnpBatch::kDblPerStream * i;
+        RA.B.w = d;
+        RA.B.uv = d + 3 * fcap;
+        RA.B.pair_q = d + 5 * fcap;
+        RA.B.pair_w = d + 8 * fcap;
+        RA.B.hyp_pose = d + 11 * fcap;
+        int* q = b.rint.p + PnpBatch::kIntPerStream * i;
+        RA.B.cam = q;
+        RA.B.pos = q + fcap;
+        RA.B.pair_ok = q + 2 * fcap;
+        RA.B.counts = q + 3 * fcap;
+        RA.B.hyp_count = b.rcount.p + n_hyp * i;
+        RA.B.samples = frames[i].samples ? reinterpret_cast<const int*>(b.dimg.p + b.samp_off[i]) : nullptr;
+        RA.B.mask = b.rmask.p + mstride * i;
+        RA.n_hyp = rc->n_hyp;
+        RA.min_inliers = rc->min_inliers;
+        RA.seed = rc->seed;
+        RA.inlier_sq = rc->inlier_sq_error;
+        RA.min_depth = rc->min_depth;
+        RA.out = b.hrobust.p + i;
+        tab[i] = RA;
+    }
+    if (want_mask && b.hmask.n < mstride * b.n) b.hmask.alloc(mstride * b.n);
+    if (want_count && b.hcount.n < n_hyp * b.n) b.hcount.alloc(n_hyp * b.n);
+    RSVIO_HIP(hipMemcpyAsync(b.dimg.p, b.himg.p, bytes, hipMemcpyHostToDevice, b.stream));
+    const RobustArgs* dtab = reinterpret_cast<const RobustArgs*>(b.dimg.p);
+    RSVIO_HIP(hipEventRecord(b.ev[0], b.stream));
+    if (cap == kPnpBatchSmallCap) {
+        hipLaunchKernelGGL(pnp_robust_join_batch_kernel<kPnpBatchSmallCap>, dim3(b.n), dim3(kPnpThreads), 0, b.stream,
+                           dtab);
+        hipLaunchKernelGGL(pnp_robust_score_batch_kernel, dim3(rc->n_hyp, b.n), dim3(64), 0, b.stream, dtab);
+        hipLaunchKernelGGL(pnp_robust_refit_batch_kernel<kPnpBatchSmallCap>, dim3(b.n), dim3(kPnpThreads), 0, b.stream,
+                           dtab);
+    } else {
+        hipLaunchKernelGGL(pnp_robust_join_batch_kernel<kPnpMaxFeatures>, dim3(b.n), dim3(kPnpThreads), 0, b.stream,
+                           dtab);
+        hipLaunchKernelGGL(pnp_robust_score_batch_kernel, dim3(rc->n_hyp, b.n), dim3(64), 0, b.stream, dtab);
+        hipLaunchKernelGGL(pnp_robust_refit_batch_kernel<kPnpMaxFeatures>, dim3(b.n), dim3(kPnpThreads), 0, b.stream,
+                           dtab);
+    }
+    RSVIO_HIP(hipGetLastError());
+    RSVIO_HIP(hipEventRecord(b.ev[1], b.stream));
+    if (want_mask && mstride)
+        RSVIO_HIP(hipMemcpyAsync(b.hmask.p, b.rmask.p, mstride * b.n, hipMemcpyDeviceToHost, b.stream));
+    if (want_count)
+        RSVIO_HIP(hipMemcpyAsync(b.hcount.p, b.rcount.p, sizeof(int32_t) * n_hyp * b.n, hipMemcpyDeviceToHost,
+                                 b.stream));
+    RSVIO_HIP(hipStreamSynchronize(b.stream));
+    float ms = 0.f;
+    RSVIO_HIP(hipEventElapsedTime(&ms, b.ev[0], b.ev[1]));
+    b.device_ms = ms;
+    if (device_ms) *device_ms = ms;
+    for (int i = 0; i < b.n; ++i) {
+        const rsvio_motion_frame& f = frames[i];
+        results[i] = b.hrobust.p[i];
+        keyframe_rule(tab[i].P, &results[i].motion);
+        results[i].device_ms = ms;
+        const uint8_t* m = b.hmask.p + mstride * i;
+        if (f.mask_l && f.n_l) std::memcpy(f.mask_l, m, f.n_l);
+        if (f.mask_r && f.n_r) std::memcpy(f.mask_r, m + f.n_l, f.n_r);
+        if (f.hyp_count) std::memcpy(f.hyp_count, b.hcount.p + n_hyp * i, sizeof(int32_t) * n_hyp);
+    }
+    return RSVIO_OK;
+}
+
 }  // namespace rsvio
 
 struct rsvio_pnp {
     rsvio::Pnp p;
+};
+
+struct rsvio_pnp_batch {
+    rsvio::PnpBatch b;
 };
 
 using rsvio::guarded;
@@ -1062,6 +1353,50 @@ int rsvio_track_motion_robust_tracker(rsvio_pnp* h, rsvio_tracker* t, const doub
         if (rc != RSVIO_OK) return rc;
         return rsvio::run_pnp_robust(P, A, P.active(), ransac, samples, mask_l, mask_r, hyp_count, res);
     });
+}
+
+int rsvio_pnp_batch_create(rsvio_pnp* const* handles, int32_t n, rsvio_pnp_batch** out) {
+    if (!handles || !out || n < 1 || n > rsvio::kPnpBatchMax) return RSVIO_ERR_INVALID_ARG;
+    std::vector<rsvio::Pnp*> h((size_t)n);
+    for (int32_t i = 0; i < n; ++i) {
+        if (!handles[i]) return RSVIO_ERR_INVALID_ARG;
+        h[i] = &handles[i]->p;
+        if (h[i]->device != h[0]->device) {
+            rsvio::set_last_error("rsvio_pnp_batch_create: the handles are on different devices");
+            return RSVIO_ERR_INVALID_ARG;
+        }
+    }
+    return guarded([&] {
+        auto* b = new rsvio_pnp_batch();
+        try {
+            b->b.init(h[0]->device, std::move(h));
+        } catch (...) {
+            delete b;
+            throw;
+        }
+        *out = b;
+        return (int)RSVIO_OK;
+    });
+}
+
+void rsvio_pnp_batch_destroy(rsvio_pnp_batch* b) { delete b; }
+
+int rsvio_pnp_batch_track_motion(rsvio_pnp_batch* b, const rsvio_motion_frame* frames, const rsvio_lm_cfg* cfg,
+                                 const rsvio_keyframe_rule* rule, rsvio_motion_result* results, double* device_ms) {
+    if (!b || !frames || !rule || !results) return RSVIO_ERR_INVALID_ARG;
+    const int rc = rsvio::batch_check(b->b, frames, cfg, "rsvio_pnp_batch_track_motion");
+    if (rc != RSVIO_OK) return rc;
+    return guarded([&] { return rsvio::run_pnp_batch(b->b, frames, cfg, rule, results, device_ms); });
+}
+
+int rsvio_pnp_batch_track_motion_robust(rsvio_pnp_batch* b, const rsvio_motion_frame* frames, const rsvio_lm_cfg* cfg,
+                                        const rsvio_keyframe_rule* rule, const rsvio_ransac_cfg* ransac,
+                                        rsvio_robust_motion_result* results, double* device_ms) {
+    if (!b || !frames || !rule || !results || !rsvio::ransac_cfg_ok(ransac)) return RSVIO_ERR_INVALID_ARG;
+    const int rc = rsvio::batch_check(b->b, frames, cfg, "rsvio_pnp_batch_track_motion_robust");
+    if (rc != RSVIO_OK) return rc;
+    return guarded(
+        [&] { return rsvio::run_pnp_batch_robust(b->b, frames, cfg, rule, ransac, results, device_ms); });
 }
 
 }  // extern "C"

@@ -21,7 +21,6 @@
 #pragma once
 
 constexpr int kRansacMaxHyp = 1024;
-constexpr int kPairSlots = 2 * kPnpMaxFeatures;  // LDS hash of the right list: load <= 1/2
 
 struct RobustBufs {
     double* w;         // [3][kPnpMaxFeatures]  the joined observations: map point (f32 widened)
@@ -152,8 +151,9 @@ __device__ __forceinline__ int block_excl_scan(int v, int* s_w, int tid, int* to
     return base + inc - v;
 }
 
+template <int CAP>
 __device__ __forceinline__ uint32_t pair_slot(uint64_t id) {
-    return (uint32_t)((id * 0x9E3779B97F4A7C15ull) >> 51) & (uint32_t)(kPairSlots - 1);
+    return (uint32_t)((id * 0x9E3779B97F4A7C15ull) >> 51) & (uint32_t)(2 * CAP - 1);
 }
 
 __device__ __forceinline__ uint64_t feature_id(const PnpArgs& A, int cam, int i) {
@@ -161,21 +161,27 @@ __device__ __forceinline__ uint64_t feature_id(const PnpArgs& A, int cam, int i)
 }
 
 // R1: join, pair and triangulate.  One workgroup; feature j of the combined list (left then right)
-// lives at LDS entry j as in the plain kernel.
-__global__ __launch_bounds__(kPnpThreads) void pnp_robust_join_kernel(RobustArgs RA) {
-    __shared__ float s_mpw[3][kPnpMaxFeatures];
-    __shared__ float s_uv[2][kPnpMaxFeatures];
-    __shared__ int8_t s_cam[kPnpMaxFeatures];   // feature -> camera, -1: no map point
-    __shared__ short s_mate[kPnpMaxFeatures];   // left feature -> its id's position in the right list, -1: none
+// lives at LDS entry j as in the plain kernel.  The bodies of R1 to R3 are shared by the
+// single-stream kernels (RA by value) and the batched ones (RA in a device table); CAP is the LDS
+// capacity in features (nf <= CAP, checked on the host), `cap` the stride of the global arrays,
+// which does not depend on it.  The pairs come out by ascending left position whatever slot of
+// the LDS hash an id takes, so CAP changes no result.
+template <int CAP>
+__device__ __forceinline__ void pnp_robust_join_body(const RobustArgs& RA) {
+    constexpr int kPairSlots = 2 * CAP;         // LDS hash of the right list: load <= 1/2
+    __shared__ float s_mpw[3][CAP];
+    __shared__ float s_uv[2][CAP];
+    __shared__ int8_t s_cam[CAP];               // feature -> camera, -1: no map point
+    __shared__ short s_mate[CAP];               // left feature -> its id's position in the right list, -1: none
     __shared__ int s_ht[kPairSlots];            // hash of the joined right features: position, -1: free
     __shared__ int s_w[kPnpWaves];
     __shared__ int s_nvalid;
     const PnpArgs& A = RA.P;
     const int tid = threadIdx.x;
-    const int n0 = A.n[0], n1 = A.n[1], nf = n0 + n1;  // nf <= kPnpMaxFeatures (checked on the host)
+    const int n0 = A.n[0], n1 = A.n[1], nf = n0 + n1;  // nf <= CAP (checked on the host)
     constexpr int cap = kPnpMaxFeatures;
     for (int s = tid; s < kPairSlots; s += kPnpThreads) s_ht[s] = -1;
-    for (int j = tid; j < cap; j += kPnpThreads) {
+    for (int j = tid; j < CAP; j += kPnpThreads) {
         s_mate[j] = -1;
         s_cam[j] = -1;
     }
@@ -197,7 +203,7 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_robust_join_kernel(RobustArgs
         s_mpw[1][j] = pw[1];
         s_mpw[2][j] = pw[2];
         if (cam == 1) {
-            uint32_t s = pair_slot(id);
+            uint32_t s = pair_slot<CAP>(id);
             for (int probe = 0; probe < kPairSlots; ++probe) {
                 const int prev = atomicCAS(&s_ht[s], -1, i);
                 if (prev == -1) break;
@@ -213,7 +219,7 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_robust_join_kernel(RobustArgs
     for (int j = tid; j < n0; j += kPnpThreads) {
         if (s_cam[j] < 0) continue;
         const uint64_t id = feature_id(A, 0, j);
-        uint32_t s = pair_slot(id);
+        uint32_t s = pair_slot<CAP>(id);
         for (int probe = 0; probe < kPairSlots; ++probe) {
             const int at = s_ht[s];
             if (at < 0) break;
@@ -225,8 +231,8 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_robust_join_kernel(RobustArgs
         }
     }
     __syncthreads();
-    // compaction in list order: thread t owns features [8 t, 8 t + 8)
-    constexpr int kChunk = cap / kPnpThreads;
+    // compaction in list order: thread t owns features [kChunk t, kChunk (t + 1))
+    constexpr int kChunk = CAP / kPnpThreads;
     const int j_lo = tid * kChunk;
     int c_obs = 0, c_pair = 0;
 #pragma unroll
@@ -276,6 +282,16 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_robust_join_kernel(RobustArgs
     }
 }
 
+__global__ __launch_bounds__(kPnpThreads) void pnp_robust_join_kernel(RobustArgs RA) {
+    pnp_robust_join_body<kPnpMaxFeatures>(RA);
+}
+
+// Batched R1: workgroup blockIdx.x is stream i
+template <int CAP>
+__global__ __launch_bounds__(kPnpThreads) void pnp_robust_join_batch_kernel(const RobustArgs* __restrict__ table) {
+    pnp_robust_join_body<CAP>(table[blockIdx.x]);
+}
+
 // The orthonormal frame of a triangle (columns e1, e2, e3 in F[3 i + c]) and its centroid; false
 // when the triangle is degenerate: |a x b|^2 <= 1e-12 |a|^2 |b|^2
 __device__ __forceinline__ bool triangle_frame(const double p[3][3], double F[9], double mean[3]) {
@@ -322,8 +338,8 @@ __device__ __forceinline__ void prior_pose(const PnpArgs& A, double x[7], double
     for (int k = 0; k < 9; ++k) R[k] = P0.R[k / 3][k % 3];
 }
 
-// R2: one wave per hypothesis
-__global__ __launch_bounds__(64) void pnp_robust_score_kernel(RobustArgs RA) {
+// R2: one wave per hypothesis (blockIdx.x)
+__device__ __forceinline__ void pnp_robust_score_body(const RobustArgs& RA) {
     const PnpArgs& A = RA.P;
     const int h = blockIdx.x, lane = threadIdx.x;
     constexpr int cap = kPnpMaxFeatures;
@@ -409,6 +425,13 @@ __global__ __launch_bounds__(64) void pnp_robust_score_kernel(RobustArgs RA) {
     }
 }
 
+__global__ __launch_bounds__(64) void pnp_robust_score_kernel(RobustArgs RA) { pnp_robust_score_body(RA); }
+
+// Batched R2 on a grid of (n_hyp, n): blockIdx.x the hypothesis, blockIdx.y the stream
+__global__ __launch_bounds__(64) void pnp_robust_score_batch_kernel(const RobustArgs* __restrict__ table) {
+    pnp_robust_score_body(table[blockIdx.y]);
+}
+
 // Unit quaternion (w, i, j, k; w >= 0) of a rotation matrix, by its largest diagonal form
 __device__ __forceinline__ void quat_of_rotation(const double* R, double* q) {
     const double tr = R[0] + R[4] + R[8];
@@ -433,11 +456,12 @@ __device__ __forceinline__ void quat_of_rotation(const double* R, double* q) {
 
 // R3: select, refit, classify.  One workgroup; the LM section is pnp_track_motion_kernel's, pass
 // for pass, over the LDS entries of the winner's inliers.
-__global__ __launch_bounds__(kPnpThreads) void pnp_robust_refit_kernel(RobustArgs RA) {
-    __shared__ float s_mpw[3][kPnpMaxFeatures];
-    __shared__ float s_uv[2][kPnpMaxFeatures];
-    __shared__ int8_t s_cam[kPnpMaxFeatures];     // feature -> camera, -1: no factor (no map point or outlier)
-    __shared__ uint8_t s_mask[kPnpMaxFeatures];
+template <int CAP>
+__device__ __forceinline__ void pnp_robust_refit_body(const RobustArgs& RA) {
+    __shared__ float s_mpw[3][CAP];
+    __shared__ float s_uv[2][CAP];
+    __shared__ int8_t s_cam[CAP];                 // feature -> camera, -1: no factor (no map point or outlier)
+    __shared__ uint8_t s_mask[CAP];
     __shared__ double s_red[kPnpWaves][kRed];
     __shared__ double s_sum[kRed];
     __shared__ double s_pose[12];
@@ -480,7 +504,7 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_robust_refit_kernel(RobustArg
         s_nin = 0;
     }
     if (tid < 32) s_tcb[tid >> 4][tid & 15] = A.TCB[tid >> 4][tid & 15];
-    for (int j = tid; j < cap; j += kPnpThreads) {
+    for (int j = tid; j < CAP; j += kPnpThreads) {
         s_cam[j] = -1;
         s_mask[j] = 0;
     }
@@ -688,4 +712,14 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_robust_refit_kernel(RobustArg
         o->reserved = 0;
         o->device_ms = 0.0;  // the host fills it from its events
     }
+}
+
+__global__ __launch_bounds__(kPnpThreads) void pnp_robust_refit_kernel(RobustArgs RA) {
+    pnp_robust_refit_body<kPnpMaxFeatures>(RA);
+}
+
+// Batched R3: workgroup blockIdx.x is stream i
+template <int CAP>
+__global__ __launch_bounds__(kPnpThreads) void pnp_robust_refit_batch_kernel(const RobustArgs* __restrict__ table) {
+    pnp_robust_refit_body<CAP>(table[blockIdx.x]);
 }

@@ -88,6 +88,15 @@ class RobustMotionResult(C.Structure):
 RANSAC_STATUS = {1: "Ok", 2: "TooFewPairs", -1: "NoConsensus"}
 
 
+class MotionFrame(C.Structure):
+    """rsvio_motion_frame (112 B): one slot's frame of rsvio_pnp_batch_track_motion*."""
+    _fields_ = [("ids_l", C.c_void_p), ("uv_l", C.c_void_p), ("n_l", C.c_size_t),
+                ("ids_r", C.c_void_p), ("uv_r", C.c_void_p), ("n_r", C.c_size_t),
+                ("T_W_B_last_kf", C.c_void_p), ("T_C_B2", C.c_void_p), ("cfg", C.POINTER(LmCfg)),
+                ("samples", C.c_void_p), ("mask_l", C.c_void_p), ("mask_r", C.c_void_p), ("hyp_count", C.c_void_p),
+                ("on_device", C.c_int32), ("id_stride", C.c_int32)]
+
+
 class BaParams(C.Structure):
     _fields_ = [("max_keyframes", C.c_int32), ("max_landmarks", C.c_int32),
                 ("max_observations", C.c_int32), ("device", C.c_int32)]
@@ -170,6 +179,12 @@ SIG = {
     "rsvio_track_motion_robust_tracker": (C.c_int, [P, P, P, P, C.POINTER(LmCfg), C.POINTER(KeyframeRule),
                                                     C.POINTER(RansacCfg), P, P, P, P,
                                                     C.POINTER(RobustMotionResult)]),
+    "rsvio_pnp_batch_create": (C.c_int, [P, C.c_int32, C.POINTER(P)]),
+    "rsvio_pnp_batch_track_motion": (C.c_int, [P, P, C.POINTER(LmCfg), C.POINTER(KeyframeRule), P,
+                                               C.POINTER(C.c_double)]),
+    "rsvio_pnp_batch_track_motion_robust": (C.c_int, [P, P, C.POINTER(LmCfg), C.POINTER(KeyframeRule),
+                                                      C.POINTER(RansacCfg), P, C.POINTER(C.c_double)]),
+    "rsvio_pnp_batch_destroy": (None, [P]),
     "rsvio_pyramid_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "rsvio_build_pyramid": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, P]),
     "rsvio_track_points": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, C.c_float,

@@ -208,3 +208,140 @@ class MotionTracker:
                                                             C.byref(self.rule), C.byref(rc), ptr(samples),
                                                             ptr(mask_l), ptr(mask_r), ptr(counts), C.byref(r)))
         return _robust_result(r, mask_l[:n_l].copy(), mask_r[:n_r].copy(), counts)
+
+
+@dataclass
+class MotionFrame:
+    """One slot's frame of a MotionBatch run (rsvio_motion_frame).  Host arrays, or -- with
+    `on_device` -- lists already on the device, read in place: `ids_l` / `ids_r` torch uint8 device
+    buffers holding the u64 ids `id_stride` bytes apart (0: 8; sizeof(rsvio_feature) for tracker
+    output), with `n_l` / `n_r` ids in them, and `uv_l` / `uv_r` float32 (n, 2) device tensors."""
+    ids_l: object
+    uv_l: object
+    ids_r: object
+    uv_r: object
+    T_W_B_last_kf: np.ndarray
+    T_C_B2: np.ndarray
+    cfg: object = None        # this slot's LM cfg (None: the call's)
+    samples: object = None    # robust only: n_hyp x 3 pair indices (None: the seeded sampler)
+    on_device: bool = False
+    id_stride: int = 0
+    n_l: int | None = None    # on_device: the number of ids (None: len(uv_l))
+    n_r: int | None = None
+
+
+def _device_list(ids, uv, n, stride):
+    """(ids pointer, uv pointer, n) of a device-resident list; the tensors must outlive the run."""
+    import torch
+    n = len(uv) if n is None else int(n)
+    if n == 0:
+        return None, None, 0
+    if not (isinstance(ids, torch.Tensor) and ids.is_cuda and ids.dtype == torch.uint8 and ids.is_contiguous()):
+        raise ValueError("on_device ids must be a contiguous torch uint8 device buffer")
+    if not (isinstance(uv, torch.Tensor) and uv.is_cuda and uv.dtype == torch.float32 and uv.is_contiguous() and
+            tuple(uv.shape) == (n, 2)):
+        raise ValueError("on_device uv must be a contiguous float32 (n, 2) device tensor")
+    if ids.numel() < (n - 1) * (stride or 8) + 8:
+        raise ValueError("on_device ids buffer is shorter than n ids at id_stride")
+    return ids.data_ptr(), uv.data_ptr(), n
+
+
+class MotionBatch:
+    """rsvio_pnp_batch: one frame per MotionTracker -- each with its own map -- tracked by one launch
+    (plain) or three (robust) with one upload and one host wait; every result is bit for bit the
+    tracker's own track_motion / track_motion_robust result.  The trackers are borrowed (they must
+    outlive the batch; the same one may sit in several slots); slot i uses trackers[i]'s current
+    map and the FIRST tracker's keyframe rule."""
+
+    def __init__(self, trackers):
+        self.trackers = list(trackers)
+        self.n = len(self.trackers)
+        arr = (C.c_void_p * max(self.n, 1))(*[t._h.value for t in self.trackers])
+        h = C.c_void_p()
+        check(_lib.load().rsvio_pnp_batch_create(arr, self.n, C.byref(h)))
+        self._h = h
+        self.rule = self.trackers[0].rule
+        self.device_ms = 0.0   # of the last run: the batch's launches by HIP events
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.load().rsvio_pnp_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _frames(self, frames, n_hyp=None):
+        """The ctypes frame table and the arrays it points into (kept alive by the caller)."""
+        if len(frames) != self.n:
+            raise ValueError(f"{len(frames)} frames for a batch of {self.n}")
+        tab = (_lib.MotionFrame * self.n)()
+        keep = []
+        for i, f in enumerate(frames):
+            c = tab[i]
+            if f.on_device:
+                c.ids_l, c.uv_l, c.n_l = _device_list(f.ids_l, f.uv_l, f.n_l, f.id_stride)
+                c.ids_r, c.uv_r, c.n_r = _device_list(f.ids_r, f.uv_r, f.n_r, f.id_stride)
+                c.on_device, c.id_stride = 1, int(f.id_stride)
+                keep.append((f.ids_l, f.uv_l, f.ids_r, f.uv_r))
+            else:
+                ids_l = np.ascontiguousarray(f.ids_l, np.uint64).reshape(-1)
+                ids_r = np.ascontiguousarray(f.ids_r, np.uint64).reshape(-1)
+                uv_l = np.ascontiguousarray(f.uv_l, np.float32).reshape(-1, 2)
+                uv_r = np.ascontiguousarray(f.uv_r, np.float32).reshape(-1, 2)
+                if len(uv_l) != len(ids_l) or len(uv_r) != len(ids_r):
+                    raise ValueError(f"slot {i}: ids and uv differ in length")
+                c.ids_l, c.uv_l, c.n_l = ptr(ids_l), ptr(uv_l), len(ids_l)
+                c.ids_r, c.uv_r, c.n_r = ptr(ids_r), ptr(uv_r), len(ids_r)
+                keep.append((ids_l, uv_l, ids_r, uv_r))
+            Tl = np.ascontiguousarray(f.T_W_B_last_kf, np.float64).reshape(16)
+            tcb = np.ascontiguousarray(f.T_C_B2, np.float64).reshape(32)
+            c.T_W_B_last_kf, c.T_C_B2 = ptr(Tl), ptr(tcb)
+            keep.append((Tl, tcb, f.cfg))
+            if f.cfg is not None:
+                c.cfg = C.pointer(f.cfg)
+            if n_hyp is not None and f.samples is not None:
+                smp = _samples(f.samples, n_hyp)
+                c.samples = ptr(smp)
+                keep.append(smp)
+        return tab, keep
+
+    def track_motion(self, frames, cfg=None) -> list[MotionResult]:
+        cfg = cfg or pnp_cfg()
+        tab, keep = self._frames(frames)
+        res = (_lib.MotionResult * self.n)()
+        ms = C.c_double(0.0)
+        check(_lib.load().rsvio_pnp_batch_track_motion(self._h, C.addressof(tab), C.byref(cfg), C.byref(self.rule),
+                                                       C.addressof(res), C.byref(ms)))
+        del keep
+        self.device_ms = ms.value
+        return [_result(r) for r in res]
+
+    def track_motion_robust(self, frames, ransac: RansacConfig | None = None, cfg=None,
+                            want_counts: bool = False, want_masks: bool = True) -> list[RobustMotionResult]:
+        """want_counts / want_masks: one bool, or one per slot; a slot without leaves its pointers
+        NULL (hyp_count, mask_l / mask_r come back None)."""
+        cfg = cfg or pnp_cfg()
+        rc = (ransac or RansacConfig()).to_c()
+        tab, keep = self._frames(frames, n_hyp=rc.n_hyp)
+        wm = [want_masks] * self.n if isinstance(want_masks, bool) else list(want_masks)
+        wc = [want_counts] * self.n if isinstance(want_counts, bool) else list(want_counts)
+        outs = []
+        for i in range(self.n):
+            c = tab[i]
+            ml = np.zeros(c.n_l, np.uint8) if wm[i] else None
+            mr = np.zeros(c.n_r, np.uint8) if wm[i] else None
+            cnt = np.zeros(max(rc.n_hyp, 0), np.int32) if wc[i] else None
+            c.mask_l, c.mask_r, c.hyp_count = ptr(ml), ptr(mr), ptr(cnt)
+            outs.append((ml, mr, cnt))
+        res = (_lib.RobustMotionResult * self.n)()
+        ms = C.c_double(0.0)
+        check(_lib.load().rsvio_pnp_batch_track_motion_robust(self._h, C.addressof(tab), C.byref(cfg),
+                                                              C.byref(self.rule), C.byref(rc), C.addressof(res),
+                                                              C.byref(ms)))
+        del keep
+        self.device_ms = ms.value
+        return [_robust_result(r, *o) for r, o in zip(res, outs)]
