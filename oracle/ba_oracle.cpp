@@ -614,9 +614,15 @@ int orc_ba_build_system(int n_kf, const double* pose7, const uint8_t* kf_fixed, 
 
 void orc_set_ba_threads(int threads) { g_ba_threads = threads < 1 ? 1 : threads; }
 
-int orc_ba_solve(int n_kf, double* pose7, const uint8_t* kf_fixed, int n_lm, double* p_W, int n_obs,
-                 const int32_t* obs_lm, const int32_t* obs_kf, const uint8_t* obs_cam,
-                 const double* obs_uv, const double* TCB2, const orc_lm_cfg* cfg, orc_ba_result* res) {
+}  // extern "C"
+
+// The LM loop behind orc_ba_solve and orc_ba_solve_trace.  With trace != nullptr it also records
+// one orc_ba_trace_row per iteration (up to trace_cap); the recording only copies values the loop
+// has computed anyway, so the solve's results do not depend on it.
+static int ba_solve_loop(int n_kf, double* pose7, const uint8_t* kf_fixed, int n_lm, double* p_W, int n_obs,
+                         const int32_t* obs_lm, const int32_t* obs_kf, const uint8_t* obs_cam,
+                         const double* obs_uv, const double* TCB2, const orc_lm_cfg* cfg, orc_ba_result* res,
+                         orc_ba_trace_row* trace, int trace_cap) {
     Problem pr = make_problem(n_kf, kf_fixed, n_lm, n_obs, obs_lm, obs_kf, obs_cam, obs_uv, TCB2, cfg->huber_delta);
     res->iterations = 0;
     // sliding_window.rs:303-319 guards
@@ -637,6 +643,11 @@ int orc_ba_solve(int n_kf, double* pose7, const uint8_t* kf_fixed, int n_lm, dou
     std::vector<double> x7t(x7), pwt(pw), dc;
     for (int it = 0; it < cfg->max_iterations; ++it) {
         res->iterations = it + 1;
+        orc_ba_trace_row* row = (trace && it < trace_cap) ? &trace[it] : nullptr;
+        if (row) {
+            const double nan = std::numeric_limits<double>::quiet_NaN();
+            *row = orc_ba_trace_row{lambda, nu, cost, nan, nan, nan, nan, 0};
+        }
         System sy = build(pr, poses, pw.data(), lambda);
         if (!std::isfinite(sy.cost)) {
             status = LM_NUMERICAL_FAILURE;
@@ -719,6 +730,7 @@ int orc_ba_solve(int n_kf, double* pose7, const uint8_t* kf_fixed, int n_lm, dou
                 for (int i = 0; i < 7; ++i) x2 += x7[7 * k + i] * x7[7 * k + i];
         for (double v : pw) x2 += v * v;
         double dxn = std::sqrt(dx2), xn = std::sqrt(x2);
+        if (row) row->step_ratio = dxn / (xn + cfg->parameter_tolerance);
         if (dxn <= cfg->parameter_tolerance * (xn + cfg->parameter_tolerance)) {
             status = LM_PARAM_TOL;
             break;
@@ -738,6 +750,11 @@ int orc_ba_solve(int n_kf, double* pose7, const uint8_t* kf_fixed, int n_lm, dou
         double pred = 0.5 * (lambda * dx2 - gdx);
         double dcost = cost - new_cost;
         double rho = dcost / pred;
+        if (row) {
+            row->new_cost = new_cost;
+            row->rho = rho;
+            row->rel_dcost = std::fabs(dcost) / cost;
+        }
         if (std::isfinite(new_cost) && std::fabs(dcost) <= cfg->cost_tolerance * cost) {
             // converged: |change| within the tolerance whatever its sign; the candidate is not
             // applied (DESIGN.md section 5 -- a rounding-level change decides nothing).  This
@@ -746,6 +763,7 @@ int orc_ba_solve(int n_kf, double* pose7, const uint8_t* kf_fixed, int n_lm, dou
             break;
         }
         if (std::isfinite(new_cost) && rho > 0.0) {
+            if (row) row->accepted = 1;
             x7.swap(x7t);
             pw.swap(pwt);
             poses.swap(tposes);
@@ -767,6 +785,23 @@ int orc_ba_solve(int n_kf, double* pose7, const uint8_t* kf_fixed, int n_lm, dou
     memcpy(pose7, x7.data(), sizeof(double) * x7.size());
     memcpy(p_W, pw.data(), sizeof(double) * pw.size());
     return 0;
+}
+
+extern "C" {
+
+int orc_ba_solve(int n_kf, double* pose7, const uint8_t* kf_fixed, int n_lm, double* p_W, int n_obs,
+                 const int32_t* obs_lm, const int32_t* obs_kf, const uint8_t* obs_cam,
+                 const double* obs_uv, const double* TCB2, const orc_lm_cfg* cfg, orc_ba_result* res) {
+    return ba_solve_loop(n_kf, pose7, kf_fixed, n_lm, p_W, n_obs, obs_lm, obs_kf, obs_cam, obs_uv, TCB2, cfg, res,
+                         nullptr, 0);
+}
+
+int orc_ba_solve_trace(int n_kf, double* pose7, const uint8_t* kf_fixed, int n_lm, double* p_W, int n_obs,
+                       const int32_t* obs_lm, const int32_t* obs_kf, const uint8_t* obs_cam,
+                       const double* obs_uv, const double* TCB2, const orc_lm_cfg* cfg, orc_ba_result* res,
+                       orc_ba_trace_row* trace, int trace_cap) {
+    return ba_solve_loop(n_kf, pose7, kf_fixed, n_lm, p_W, n_obs, obs_lm, obs_kf, obs_cam, obs_uv, TCB2, cfg, res,
+                         trace, trace_cap);
 }
 
 }  // extern "C"

@@ -28,6 +28,12 @@ class BaResult(C.Structure):
                 ("final_cost", C.c_double)]
 
 
+class BaTraceRow(C.Structure):
+    _fields_ = [("lam", C.c_double), ("nu", C.c_double), ("cost", C.c_double), ("new_cost", C.c_double),
+                ("rho", C.c_double), ("rel_dcost", C.c_double), ("step_ratio", C.c_double),
+                ("accepted", C.c_int)]
+
+
 class OrcFeature(C.Structure):
     _fields_ = [("id", C.c_uint64), ("x", C.c_float), ("y", C.c_float), ("aff", C.c_float * 6)]
 
@@ -91,6 +97,8 @@ _SIG = {
                                       C.c_double, P, P, C.POINTER(C.c_double)]),
     "orc_ba_solve": (C.c_int, [C.c_int, P, P, C.c_int, P, C.c_int, P, P, P, P, P, C.POINTER(LmCfg),
                                C.POINTER(BaResult)]),
+    "orc_ba_solve_trace": (C.c_int, [C.c_int, P, P, C.c_int, P, C.c_int, P, P, P, P, P, C.POINTER(LmCfg),
+                                     C.POINTER(BaResult), P, C.c_int]),
     "orc_se3_plus": (None, [P, P, P]),
     "orc_quat_from_rotation": (None, [P, P]),
     "orc_quat_from_matrix": (None, [P, P]),
@@ -295,6 +303,28 @@ def ba_solve(prob, cfg=None):
     load().orc_ba_solve(pose.shape[0], _p(pose), _p(a[1]), pw.shape[0], _p(pw), len(a[3]), _p(a[3]), _p(a[4]),
                         _p(a[5]), _p(a[6]), _p(a[7]), C.byref(cfg), C.byref(res))
     return pose, pw, res
+
+
+def ba_solve_trace(prob, cfg=None):
+    """ba_solve plus one dict per LM iteration started: lam and nu before the decision, cost,
+    new_cost, rho, rel_dcost = |dcost| / cost, step_ratio = dxn / (xn + parameter_tolerance) and
+    accepted.  Fields an iteration never reached (it ended on the parameter tolerance or a failed
+    linear solve) are NaN.  Returns (pose7, p_W, BaResult, rows)."""
+    cfg = cfg or lm_cfg()
+    a = _problem_arrays(prob)
+    pose = a[0].copy()
+    pw = a[2].copy()
+    res = BaResult()
+    cap = max(int(cfg.max_iterations), 1)
+    rows = (BaTraceRow * cap)()
+    load().orc_ba_solve_trace(pose.shape[0], _p(pose), _p(a[1]), pw.shape[0], _p(pw), len(a[3]), _p(a[3]),
+                              _p(a[4]), _p(a[5]), _p(a[6]), _p(a[7]), C.byref(cfg), C.byref(res),
+                              C.cast(rows, P), cap)
+    names = [f[0] for f in BaTraceRow._fields_]
+    trace = [{k: getattr(rows[i], k) for k in names} for i in range(min(res.iterations, cap))]
+    for t in trace:
+        t["accepted"] = bool(t["accepted"])
+    return pose, pw, res, trace
 
 
 def ba_build_system(prob, lam, huber_delta=2.0):

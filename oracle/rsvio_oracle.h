@@ -210,6 +210,24 @@ int orc_ba_solve(int n_kf, double* pose7, const uint8_t* kf_fixed,
                  const uint8_t* obs_cam, const double* obs_uv, const double* T_C_B2,
                  const orc_lm_cfg* cfg, orc_ba_result* res);
 
+/* orc_ba_solve with one row per LM iteration started (the same loop; orc_ba_solve's results are
+ * bit-identical).  lambda and nu are the values before the iteration's decision, cost the accepted
+ * cost entering it.  An iteration that ends before its trial is evaluated (parameter tolerance,
+ * a failed linear solve) leaves the later fields NaN.  At most trace_cap rows are written. */
+typedef struct {
+    double lambda, nu;
+    double cost, new_cost, rho;
+    double rel_dcost;   /* |cost - new_cost| / cost */
+    double step_ratio;  /* dxn / (xn + parameter_tolerance) */
+    int accepted;       /* 1: the trial became the state */
+} orc_ba_trace_row;
+int orc_ba_solve_trace(int n_kf, double* pose7, const uint8_t* kf_fixed,
+                       int n_lm, double* p_W,
+                       int n_obs, const int32_t* obs_lm, const int32_t* obs_kf,
+                       const uint8_t* obs_cam, const double* obs_uv, const double* T_C_B2,
+                       const orc_lm_cfg* cfg, orc_ba_result* res,
+                       orc_ba_trace_row* trace, int trace_cap);
+
 /* SE3 right-plus used by the LM update: pose7 <- pose7 (+) delta ([rho; theta]) */
 void orc_se3_plus(const double* pose7, const double* delta, double* out7);
 

@@ -423,6 +423,46 @@ def ba_pattern_problem(name: str, n_kf: int) -> BAProblem:
     return ba_problem_from_visibility(vis, cam, fixed, seed=100 + n_kf, init_seed=200 + n_kf)
 
 
+# The windows of the LM-path tests (tests/test_ba_lm_paths_*.py): each the smallest ba_problem that
+# still has two K6 waves (5 keyframes, 96 landmarks, 768 observations) or crosses the
+# 10-free-keyframe boundary of the camera solve (12 keyframes, 192 landmarks, 1536 observations),
+# with an initial state far enough from the optimum for the LM loop to reject steps.  What the
+# oracle does on each is pinned in tests/test_ba_lm_paths_cpu.py.
+_LM_SMALL = dict(n_kf=5, n_lm=96, kf_per_lm=4, seed=33, init_seed=34)
+_LM_WINDOWS = {
+    "default5": _LM_SMALL,                                                   # every step accepted
+    "default4": dict(_LM_SMALL, n_kf=4),
+    "W1": dict(_LM_SMALL, pose_noise=(0.3, 0.15), depth_noise=0.6),        # rejects its third step
+    "W3": dict(n_kf=12, n_lm=192, kf_per_lm=4, seed=126, init_seed=127, pose_noise=(0.3, 0.15), depth_noise=0.6),
+    "W3b": dict(n_kf=12, n_lm=192, kf_per_lm=4, seed=60, init_seed=61, pose_noise=(0.3, 0.15), depth_noise=0.6),
+    "W5": dict(n_kf=12, n_lm=192, kf_per_lm=4, seed=58, init_seed=59, pose_noise=(0.5, 0.25), depth_noise=0.8),
+    "skipped2": dict(n_kf=2, n_lm=1, kf_per_lm=1, seed=1),                  # too few residuals
+}
+
+
+def ba_outlier_window(n_outliers: int = 76, spread: float = 0.3, seed: int = 1) -> BAProblem:
+    """W2: the default 5-keyframe window with n_outliers of its 768 observations
+    (default_rng(seed).choice, without replacement) displaced by U(-spread, spread) in each
+    normalised coordinate, then narrowed to f32 and widened again as ba_problem's observations
+    are.  Roughly a tenth of the residuals are gross outliers: Huber weights below 1 inside the
+    solve at a small delta, rejected steps at delta = 2."""
+    prob = ba_problem(**_LM_SMALL)
+    rng = np.random.default_rng(seed)
+    idx = rng.choice(prob.n_obs, n_outliers, replace=False)
+    uv = prob.obs_uv.copy()
+    uv[idx] += rng.uniform(-spread, spread, (n_outliers, 2))
+    prob.obs_uv = uv.astype(np.float32).astype(np.float64)
+    return prob
+
+
+def ba_lm_window(name: str) -> BAProblem:
+    """A named window of the LM-path tests: "W1", "W2", "W3", "W3b", "W5", "default5" (W4's),
+    "default4" and "skipped2"."""
+    if name == "W2":
+        return ba_outlier_window()
+    return ba_problem(**_LM_WINDOWS[name])
+
+
 def eucm_project(params, xy: np.ndarray) -> np.ndarray:
     """EUCM projection (Khomutenko et al.; camera-intrinsic-model's EUCM, src/datasets/mod.rs:102-113)
     of the rays (x, y, 1): u = fx x / (alpha d + (1 - alpha) z) + cx, d = sqrt(beta (x^2 + y^2) + z^2).
