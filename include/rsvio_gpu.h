@@ -684,6 +684,51 @@ int rsvio_pnp_batch_track_motion_robust(rsvio_pnp_batch* b, const rsvio_motion_f
                                         rsvio_robust_motion_result* results, double* device_ms);
 void rsvio_pnp_batch_destroy(rsvio_pnp_batch* b);
 
+/* Batched tracker (the serving mode's first leg): n StereoPatchTracker handles and ONE stereo frame
+ * per handle tracked by one call -- one upload (the staged host images and the descriptor tables),
+ * three launches whatever n is (pyramids + FAST-9 of all 2n images; one LK launch of up to 3n
+ * batches: cam0 and cam1 temporal of the streams with history, every stream's stereo cell jobs;
+ * append / pack with workgroup i = stream i), one read-back and one host wait.  frames[i]'s lists,
+ * n_l, n_r and status are exactly -- byte for byte, ids included -- what
+ * rsvio_tracker_process_frame[_device] returns for that frame on handle i, and the handle is left in
+ * the state that call leaves (pyramid ping-pong, track maps, counts, output slot), so batch calls and
+ * single calls may alternate on a handle, and rsvio_tracker_undistorted, rsvio_tracker_remove_ids,
+ * rsvio_track_motion_tracker and rsvio_tracker_device_lists see the batch's frame as the last
+ * collected one.  Streams on their first frame and streams with history mix in one call.  A slot's
+ * RSVIO_ERR_CAPACITY (lists still consistent) is reported in its status and does not fail the call.
+ *   The batch borrows the handles (they must outlive it): 1 <= n <= 1024, all on one device with
+ * equal rsvio_tracker_params, each handle in ONE slot only (the call writes its state); it runs on a
+ * stream of its own.  Host images (on_device = 0; `stride` bytes per row, 0 meaning width) are
+ * staged into the batch's one upload; device images (on_device = 1) are tightly packed, complete on
+ * the device before the call, and read in place.  out_l / out_r NULL with capacity 0: that list is
+ * not copied to the host (not an error) and n_l / n_r report the device list's length.
+ *   Everything is checked before anything is launched or written: a NULL argument, n out of range,
+ * a NULL or repeated handle, unequal parameters or devices, a handle with a submitted frame not yet
+ * collected, a NULL image, a host stride below the width (a device stride other than 0 or the
+ * width) are RSVIO_ERR_INVALID_ARG and rsvio_last_error names the slot.  *device_ms (may be NULL):
+ * the call's launches by HIP events. */
+typedef struct rsvio_tracker_batch rsvio_tracker_batch;
+typedef struct {
+    const uint8_t* left;  const uint8_t* right;  /* w x h u8 each */
+    size_t stride;                /* host images: bytes per row (>= width); device images: 0 or width */
+    rsvio_feature* out_l; size_t cap_l;          /* host lists; NULL with cap 0: not copied, not an error */
+    rsvio_feature* out_r; size_t cap_r;
+    size_t n_l, n_r;              /* out: as process_frame's *n_l, *n_r (device list length when not copied) */
+    int32_t on_device;            /* 0: host images (staged into the batch's one upload); 1: device pointers */
+    int32_t status;               /* out: what rsvio_tracker_process_frame would have returned for this slot */
+} rsvio_stereo_frame;
+int rsvio_tracker_batch_create(rsvio_tracker* const* handles, int32_t n, rsvio_tracker_batch** out);
+int rsvio_tracker_batch_process_frames(rsvio_tracker_batch* b, rsvio_stereo_frame* frames, double* device_ms);
+void rsvio_tracker_batch_destroy(rsvio_tracker_batch* b);
+/* The last collected frame's lists in place on the device (valid until the handle's next-but-one
+ * frame, which writes the same output slot): AoS rsvio_feature lists and, with cameras attached
+ * (rsvio_tracker_set_cameras), the fused undistorted coordinates as float pairs (NULL without) --
+ * e.g. an rsvio_motion_frame with on_device = 1 and id_stride = sizeof(rsvio_feature).  d_uv_l and
+ * d_uv_r may be NULL. */
+int rsvio_tracker_device_lists(rsvio_tracker* t, const rsvio_feature** d_l, size_t* n_l,
+                               const rsvio_feature** d_r, size_t* n_r,
+                               const float** d_uv_l, const float** d_uv_r);
+
 #ifdef __cplusplus
 }
 #endif

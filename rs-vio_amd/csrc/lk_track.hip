@@ -485,6 +485,13 @@ __global__ __launch_bounds__(64) void lk_track_kernel(TrackLaunch P) {
         idx = job - P.tstart[lo];
         if (idx < 0 || idx >= d.n) return;  // a malformed caller prefix never indexes out of a batch
         pyr0 = d.d_pyr0; pyr1 = d.d_pyr1; ain = d.d_aff_in; aout = d.d_aff_out; valid = d.d_valid;
+        if (P.tmask != nullptr) {
+            const int4* m = P.tmask[lo];
+            if (m != nullptr && m[idx].w == 0) {  // an empty job, as by value below
+                if (threadIdx.x == 0) valid[idx] = 0;
+                return;
+            }
+        }
     } else {
         int b = 0;
         while (b + 1 < P.nb && job >= P.start[b + 1]) ++b;

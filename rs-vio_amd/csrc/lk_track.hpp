@@ -26,6 +26,9 @@ struct TrackLaunch {
     // prefix of their sizes come from device memory and nb may exceed kMaxTrackBatches
     const rsvio_track_batch* table;
     const int32_t* tstart;
+    // table mode's job masks (the batched tracker's stereo cell jobs): a device array of nb mask
+    // pointers, entry b as mask[] above for table batch b (null entry: no mask); null: none
+    const int4* const* tmask;
     int njobs;  // set by enqueue_track: jobs in this launch
 };
 

@@ -62,7 +62,12 @@ __global__ __launch_bounds__(256) void pyramid_kernel(PyrLaunch L, PyrIO io) {
     {  // the FAST workgroups after the pyramid's (image 0 only)
         const int fb = (int)blockIdx.x - (L.copy_blocks + L.tile_start[L.levels]);
         if (fb >= 0) {
-            if (img == 0 && fb < io.fast_cells) {
+            if (io.table != nullptr) {
+                const PyrSlot d = io.table[img];
+                if (d.fast_pt != nullptr && fb < io.fast_cells)
+                    fast_cell(d.src, io.fg, fb, nullptr, nullptr, 0, d.fast_pt, d.fast_aff,
+                              reinterpret_cast<uint8_t*>(smem));
+            } else if (img == 0 && fb < io.fast_cells) {
                 const uint8_t* s0 = io.psrc ? io.psrc : io.src[0];
                 fast_cell(s0, io.fg, fb, nullptr, nullptr, 0, io.fast_pt, io.fast_aff,
                           reinterpret_cast<uint8_t*>(smem));
@@ -70,8 +75,10 @@ __global__ __launch_bounds__(256) void pyramid_kernel(PyrLaunch L, PyrIO io) {
             return;
         }
     }
-    const uint8_t* __restrict__ src = io.psrc ? io.psrc + (size_t)img * L.w * L.h : io.src[img];
-    uint8_t* __restrict__ dst_base = io.psrc ? io.pdst + (size_t)img * L.pyr_bytes : io.dst[img];
+    const uint8_t* __restrict__ src =
+        io.table ? io.table[img].src : (io.psrc ? io.psrc + (size_t)img * L.w * L.h : io.src[img]);
+    uint8_t* __restrict__ dst_base =
+        io.table ? io.table[img].dst : (io.psrc ? io.pdst + (size_t)img * L.pyr_bytes : io.dst[img]);
     int b = blockIdx.x;
     const bool aligned = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst_base)) & 15) == 0;
     // level-0 copy blocks first (16 B per lane)
@@ -260,7 +267,7 @@ void PyramidPlan::init(int w_, int h_, int levels_) {
 
 void PyramidPlan::enqueue(const PyrIO& io, int n_img, hipStream_t s) const {
     if (n_img <= 0) return;
-    if (n_img > (io.psrc ? 65535 : kMaxPyrIO)) throw std::invalid_argument("too many images per pyramid launch");
+    if (n_img > (io.psrc || io.table ? 65535 : kMaxPyrIO)) throw std::invalid_argument("too many images per pyramid launch");
     const size_t lds = io.fast_cells > 0 ? std::max(lds_bytes, (size_t)io.fg.g * io.fg.g) : lds_bytes;
     hipLaunchKernelGGL(pyramid_kernel, dim3(total_blocks + std::max(io.fast_cells, 0), n_img), dim3(256), lds, s,
                        launch, io);

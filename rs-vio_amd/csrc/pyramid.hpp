@@ -39,6 +39,14 @@ struct PyrLaunch {
 };
 
 constexpr int kMaxPyrIO = 8;
+// table mode (the batched tracker): image i's source, pyramid and -- when fast_pt is set -- the
+// outputs of FAST-9 on its grid cells, read from device memory
+struct PyrSlot {
+    const uint8_t* src;
+    uint8_t* dst;
+    int4* fast_pt;
+    float* fast_aff;
+};
 struct PyrIO {
     const uint8_t* src[kMaxPyrIO];
     uint8_t* dst[kMaxPyrIO];
@@ -51,6 +59,9 @@ struct PyrIO {
     GridGeom fg;
     int4* fast_pt;
     float* fast_aff;
+    // table mode (any number of images): per-image I/O from a device table of n_img PyrSlot; FAST
+    // (fast_cells, fg) then runs on every image whose slot has fast_pt set
+    const PyrSlot* table;
 };
 
 struct PyramidPlan {

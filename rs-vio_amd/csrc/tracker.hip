@@ -111,15 +111,15 @@ struct CamPair {
 // appended in cell scan order with consecutive ids (feature_tracker.rs:143-170, canonical order); (3) get_track_points packing, with the
 // Frame::add_{left,right}_feature unprojection fused (frame.rs:118-119,131-132).  tracked = 0
 // (first frame): the maps are taken as they are (counts = n0, n1).
-__global__ __launch_bounds__(1024) void append_pack_kernel(
-    GridGeom G, int* __restrict__ bins, int n0, int n1, int tracked, const float* __restrict__ at0, const float* __restrict__ at1,
+__device__ __forceinline__ void append_pack(
+    const GridGeom& G, int* __restrict__ bins, int n0, int n1, int tracked, const float* __restrict__ at0, const float* __restrict__ at1,
     const uint8_t* __restrict__ tv0, const uint8_t* __restrict__ tv1, uint64_t* __restrict__ ids_tmp,
     const int4* __restrict__ cell_pt, int n_cells, const float* __restrict__ new_aff0,
     const float* __restrict__ new_aff1, const uint8_t* __restrict__ new_valid, float* __restrict__ map_aff0,
     float* __restrict__ map_aff1, uint64_t* __restrict__ ids0, uint64_t* __restrict__ ids1,
     int* __restrict__ counts, unsigned long long* __restrict__ last_id, int capacity,
     rsvio_feature* __restrict__ out0, rsvio_feature* __restrict__ out1, int* __restrict__ overflow,
-    CamPair cams, float2* __restrict__ und0, float2* __restrict__ und1) {
+    const CamPair& cams, float2* __restrict__ und0, float2* __restrict__ und1) {
     __shared__ int sh[1024];
     const int tid = threadIdx.x;
     int cnt[2] = {n0, n1};
@@ -212,6 +212,22 @@ __global__ __launch_bounds__(1024) void append_pack_kernel(
             (c == 0 ? und0 : und1)[i] = make_float2(u.x, u.y);
         }
     }
+}
+
+// The single-stream launch: append_pack with its arguments by value (one workgroup).  The batched
+// tracker's launch reads them from a device descriptor per workgroup (tracker_batch.hpp).
+__global__ __launch_bounds__(1024) void append_pack_kernel(
+    GridGeom G, int* __restrict__ bins, int n0, int n1, int tracked, const float* __restrict__ at0, const float* __restrict__ at1,
+    const uint8_t* __restrict__ tv0, const uint8_t* __restrict__ tv1, uint64_t* __restrict__ ids_tmp,
+    const int4* __restrict__ cell_pt, int n_cells, const float* __restrict__ new_aff0,
+    const float* __restrict__ new_aff1, const uint8_t* __restrict__ new_valid, float* __restrict__ map_aff0,
+    float* __restrict__ map_aff1, uint64_t* __restrict__ ids0, uint64_t* __restrict__ ids1,
+    int* __restrict__ counts, unsigned long long* __restrict__ last_id, int capacity,
+    rsvio_feature* __restrict__ out0, rsvio_feature* __restrict__ out1, int* __restrict__ overflow,
+    CamPair cams, float2* __restrict__ und0, float2* __restrict__ und1) {
+    append_pack(G, bins, n0, n1, tracked, at0, at1, tv0, tv1, ids_tmp, cell_pt, n_cells, new_aff0, new_aff1,
+                new_valid, map_aff0, map_aff1, ids0, ids1, counts, last_id, capacity, out0, out1, overflow, cams,
+                und0, und1);
 }
 
 // StereoPatchTracker::remove_id (feature_tracker.rs:201-206)
@@ -502,6 +518,8 @@ TrackerView tracker_view(rsvio_tracker* h) {
 }  // namespace rsvio
 
 using rsvio::guarded;
+
+#include "tracker_batch.hpp"
 
 extern "C" {
 

@@ -97,6 +97,13 @@ class MotionFrame(C.Structure):
                 ("on_device", C.c_int32), ("id_stride", C.c_int32)]
 
 
+class StereoFrame(C.Structure):
+    """rsvio_stereo_frame (80 B): one slot's frame of rsvio_tracker_batch_process_frames."""
+    _fields_ = [("left", C.c_void_p), ("right", C.c_void_p), ("stride", C.c_size_t),
+                ("out_l", C.c_void_p), ("cap_l", C.c_size_t), ("out_r", C.c_void_p), ("cap_r", C.c_size_t),
+                ("n_l", C.c_size_t), ("n_r", C.c_size_t), ("on_device", C.c_int32), ("status", C.c_int32)]
+
+
 class BaParams(C.Structure):
     _fields_ = [("max_keyframes", C.c_int32), ("max_landmarks", C.c_int32),
                 ("max_observations", C.c_int32), ("device", C.c_int32)]
@@ -185,6 +192,11 @@ SIG = {
     "rsvio_pnp_batch_track_motion_robust": (C.c_int, [P, P, C.POINTER(LmCfg), C.POINTER(KeyframeRule),
                                                       C.POINTER(RansacCfg), P, C.POINTER(C.c_double)]),
     "rsvio_pnp_batch_destroy": (None, [P]),
+    "rsvio_tracker_batch_create": (C.c_int, [P, C.c_int32, C.POINTER(P)]),
+    "rsvio_tracker_batch_process_frames": (C.c_int, [P, P, C.POINTER(C.c_double)]),
+    "rsvio_tracker_batch_destroy": (None, [P]),
+    "rsvio_tracker_device_lists": (C.c_int, [P, C.POINTER(P), C.POINTER(C.c_size_t), C.POINTER(P),
+                                             C.POINTER(C.c_size_t), C.POINTER(P), C.POINTER(P)]),
     "rsvio_pyramid_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "rsvio_build_pyramid": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, P]),
     "rsvio_track_points": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, C.c_float,

@@ -215,7 +215,8 @@ class MotionFrame:
     """One slot's frame of a MotionBatch run (rsvio_motion_frame).  Host arrays, or -- with
     `on_device` -- lists already on the device, read in place: `ids_l` / `ids_r` torch uint8 device
     buffers holding the u64 ids `id_stride` bytes apart (0: 8; sizeof(rsvio_feature) for tracker
-    output), with `n_l` / `n_r` ids in them, and `uv_l` / `uv_r` float32 (n, 2) device tensors."""
+    output), with `n_l` / `n_r` ids in them, and `uv_l` / `uv_r` float32 (n, 2) device tensors -- or
+    all four as device addresses (ints, e.g. StereoPatchTracker.device_lists()) with `n_l` / `n_r`."""
     ids_l: object
     uv_l: object
     ids_r: object
@@ -233,9 +234,13 @@ class MotionFrame:
 def _device_list(ids, uv, n, stride):
     """(ids pointer, uv pointer, n) of a device-resident list; the tensors must outlive the run."""
     import torch
+    if n is None and isinstance(uv, int):
+        raise ValueError("on_device lists given as addresses need n_l / n_r")
     n = len(uv) if n is None else int(n)
     if n == 0:
         return None, None, 0
+    if isinstance(ids, int) and isinstance(uv, int):   # raw device addresses (StereoPatchTracker.device_lists)
+        return ids, uv, n
     if not (isinstance(ids, torch.Tensor) and ids.is_cuda and ids.dtype == torch.uint8 and ids.is_contiguous()):
         raise ValueError("on_device ids must be a contiguous torch uint8 device buffer")
     if not (isinstance(uv, torch.Tensor) and uv.is_cuda and uv.dtype == torch.float32 and uv.is_contiguous() and

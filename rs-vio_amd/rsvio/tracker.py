@@ -182,3 +182,96 @@ class StereoPatchTracker:
             out[:len(keep)] = keep
             n.append(len(keep))
         self._n = tuple(n)
+
+    def device_lists(self):
+        """rsvio_tracker_device_lists: the last collected frame's lists in place on the device, as
+        (d_left, n_left, d_right, n_right, d_uv_left, d_uv_right) -- device addresses of the AoS
+        rsvio_feature lists (ids 32 bytes apart) and, with cameras attached, of the undistorted
+        float pairs (None without).  Valid until this tracker's next-but-one frame."""
+        dl, dr, ul, ur = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        nl, nr = C.c_size_t(0), C.c_size_t(0)
+        check(_lib.load().rsvio_tracker_device_lists(self._h, C.byref(dl), C.byref(nl), C.byref(dr), C.byref(nr),
+                                                     C.byref(ul), C.byref(ur)))
+        return dl.value, nl.value, dr.value, nr.value, ul.value, ur.value
+
+
+def _image(img, h, w, slot):
+    """(pointer, stride, on_device, keep-alive) of one H x W u8 image: a numpy array whose rows are
+    contiguous (any row stride >= W) or a contiguous torch uint8 device tensor."""
+    if not isinstance(img, np.ndarray) and hasattr(img, "data_ptr"):
+        if not (img.is_cuda and img.is_contiguous() and tuple(img.shape) == (h, w) and img.element_size() == 1):
+            raise ValueError(f"slot {slot}: device images must be contiguous {h}x{w} uint8 tensors")
+        return img.data_ptr(), 0, 1, img
+    a = np.asarray(img)
+    if a.dtype != np.uint8 or a.shape != (h, w):
+        raise ValueError(f"slot {slot}: expected a {h}x{w} uint8 image")
+    if a.strides[1] != 1 or a.strides[0] < w:
+        a = np.ascontiguousarray(a)
+    return a.__array_interface__["data"][0], a.strides[0], 0, a
+
+
+class TrackerBatch:
+    """rsvio_tracker_batch: one stereo frame per StereoPatchTracker tracked by one call -- one upload,
+    three launches whatever the number of trackers, one read-back and one host wait; every list is
+    byte for byte the tracker's own process_frame result, and each tracker is left as that call
+    leaves it (batch and single calls may alternate).  The trackers are borrowed (they must outlive
+    the batch; equal parameters, one device, each in one slot only)."""
+
+    def __init__(self, trackers):
+        self.trackers = list(trackers)
+        self.n = len(self.trackers)
+        arr = (C.c_void_p * max(self.n, 1))(*[t._h.value for t in self.trackers])
+        h = C.c_void_p()
+        check(_lib.load().rsvio_tracker_batch_create(arr, self.n, C.byref(h)))
+        self._h = h
+        self.status = [0] * self.n   # per slot, of the last call: what process_frame would have returned
+        self.device_ms = 0.0         # of the last call: its launches by HIP events
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.load().rsvio_tracker_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _frames(self, lefts, rights):
+        """The ctypes frame table (lists into each tracker's cached arrays) and what it points into."""
+        if len(lefts) != self.n or len(rights) != self.n:
+            raise ValueError(f"{len(lefts)} + {len(rights)} images for a batch of {self.n}")
+        tab = (_lib.StereoFrame * self.n)()
+        keep = []
+        for i, (t, left, right) in enumerate(zip(self.trackers, lefts, rights)):
+            pl, sl, dl, kl = _image(left, t.height, t.width, i)
+            pr, sr, dr, kr = _image(right, t.height, t.width, i)
+            if dl != dr:
+                raise ValueError(f"slot {i}: one image on the host, the other on the device")
+            if not dl and sl != sr:   # one row stride per frame
+                kr = np.ascontiguousarray(kr)
+                kl = np.ascontiguousarray(kl)
+                pl, pr, sl = kl.__array_interface__["data"][0], kr.__array_interface__["data"][0], t.width
+            c = tab[i]
+            c.left, c.right, c.stride, c.on_device = pl, pr, sl, dl
+            c.out_l, c.cap_l, c.out_r, c.cap_r = ptr(t._out_l), t.cap, ptr(t._out_r), t.cap
+            keep.append((kl, kr))
+        return tab, keep
+
+    def process_frames(self, lefts, rights):
+        """[(left_features, right_features)] per slot, as each tracker's process_frame returns them.
+        A slot's RSVIO_ERR_CAPACITY is reported in .status[i] (its lists are still consistent) and
+        does not raise."""
+        tab, keep = self._frames(lefts, rights)
+        ms = C.c_double(0.0)
+        rc = _lib.load().rsvio_tracker_batch_process_frames(self._h, C.addressof(tab), C.byref(ms))
+        check(rc)
+        del keep
+        self.device_ms = ms.value
+        self.status = [int(c.status) for c in tab]
+        out = []
+        for t, c in zip(self.trackers, tab):
+            t._n = (int(c.n_l), int(c.n_r))
+            out.append((t._out_l[:c.n_l].copy(), t._out_r[:c.n_r].copy()))
+        return out

@@ -83,6 +83,8 @@ GROUPS = {
     "rsvio_pnp_create": "SlidingWindow::track_motion + keyframe rule (sliding_window.rs:490-587, estimator.rs:195-234)",
     "rsvio_quat_from_matrix": "host-only: UnitQuaternion::from_matrix (:221), window build / apply (:174-300, :418-486)",
     "rsvio_pnp_set_stream": "motion tracking (continued)",
+    "rsvio_tracker_batch_create": "batched tracker: one stereo frame per handle, many handles per call; the last "
+                                  "frame's lists on the device",
 }
 
 
