@@ -30,6 +30,16 @@
 //   single rank: the last K6 wave to arrive takes the LM decision (gain ratio, accept / reject
 //   = buffer flip, lambda, termination)
 // Every reduction has a fixed order (no floating-point atomics): results are run-to-run identical.
+//
+// One translation unit.  Fragments of it, included where their stage stands in this file (a
+// fragment is not a header of its own: it needs what precedes its include):
+//   ba_k5_panel.hpp     K5 on the matrix cores, 8-column panels (<= 10 free keyframes)
+//   ba_k5_x2.hpp        K5 on the VALU, two rows per lane (11..20 free keyframes)
+//   ba_landmarks.hpp    triangulation and the depth / reprojection gate
+//   ba_covariance.hpp   pose and landmark covariance
+// and, standing alone, ba_dispatch.hpp (host: n_free -> the K5 templates' NF).  The other stages
+// are still here, in the order of the map above, and are to move out one stage per change, each
+// shown to leave the device code alone by tools/isa_compare.py.
 #include <rccl/rccl.h>
 
 #include <algorithm>
@@ -45,6 +55,7 @@
 
 #include "common.hpp"
 
+#include "ba_dispatch.hpp"  // host: n_free -> the camera-solve templates' NF
 #include "ba_envelope.hpp"  // host: the camera system's symbolic envelope
 #include "obs_pass.hpp"  // host: set_problem's observation pass
 #include "se3.hpp"
@@ -1812,540 +1823,13 @@ __global__ __launch_bounds__(kK5Threads) void ba_camera_solve(Geometry G, Prob P
     RTSTAMP(5);
 }
 
-// ---------------------------------------------------------------------------------------
-// K5 on the matrix cores (n <= 60; RSVIO_K5=mfma): blocked right-looking
-// LDL^T of the camera system with 16-column panels.  The system (padded to NPP = 16 ceil(n/16)
-// with identity rows / columns, which couple to nothing) sits column-major in LDS.  Per panel:
-//   * wave 0 (lane = row) factors the panel's columns in registers -- per pivot K the 1/d_K
-//     chain (v_rcp_f64 + the folded Newton step), l = u / d_K, the in-panel updates from
-//     readlanes of the unscaled column, and b_i -= l_iK b_K (so b ends as L^-1 b) -- and writes
-//     L into the panel's columns of M, U = D L into Up;
-//   * every wave then updates its share of the trailing lower tiles (I, J > panel) with
-//     v_mfma_f64_16x16x4_f64: C_IJ += (-U_I) L_J^T over the panel's 16 columns (4 MFMAs per
-//     tile, accumulator in registers, C loaded from / stored to M).
-// The serial chain is the pivots inside the panels; the O(n^3) trailing work runs on the matrix
-// cores, off wave 0's chain.  z = D^-1 L^-1 b, then L^T x = z by wave 0 (readlanes, as pipe4).
-// Tolerance parity like pipe4 (same pivots; the trailing sums reassociated by the MFMA).
-// ---------------------------------------------------------------------------------------
-typedef double mf_dbl4 __attribute__((ext_vector_type(4)));
-constexpr int kMfLd = 65;  // f64 leading dimension of the LDS matrices (odd: column reads spread banks)
-constexpr int kBkLd = 129;  // the same for the 6x6-block solver past 10 free keyframes (up to 121 rows)
-// the block solver's instantiations past 10 free keyframes (a window pads up to the next one)
-inline int bk_template_nf(int n_free) { return n_free <= 13 ? 13 : n_free <= 16 ? 16 : 20; }
-constexpr int kMfPanel = 8;  // panel width: 8 pivots of in-panel VALU work between matrix-core updates
-
-// The augmented system [[S, .], [b^T, .]] padded to NPP = 16 NT >= NP + 1 rows: row NP is b, so
-// eliminating the augmented matrix turns row NP into z^T = (D^-1 L^-1 b)^T on the fly (one more
-// row of every panel).  Rows past NP are never initialised: elimination is row-local (a row's
-// update uses its own multiplier and the pivot rows' values), so they cannot leak into the
-// result; the same holds for the upper halves of the diagonal tiles.
-template <int NF>
-struct MfDims {
-    static constexpr int NP = 6 * NF;
-    static constexpr int NT = NP / 16 + 1;
-    static constexpr int NPP = 16 * NT;
-    static constexpr int NH = (NP + kMfPanel - 1) / kMfPanel;  // panels
-};
-
-// Per packed-system entry (sys layout: n_pb x 36 S | 6 n_free b | 6 n_free g_c) its destination
-// in K5's LDS: >= 0 a column-major position of M (bit 30: + lambda after the sum), -1 none (the
-// upper half of a diagonal block), -2 - i the i-th g_c.  Built on the host per problem.
-constexpr int kMfMapLambda = 1 << 30;
-inline void mf_dense_map(int nf, int n_pb, const int* pb_fa, const int* pb_fb, int* map, int np_target = 0,
-                         int ld = kMfLd) {
-    const int np = np_target > 0 ? np_target : 6 * nf;  // the b row (the template's NP)
-    for (int pb = 0; pb < n_pb; ++pb)
-        for (int k = 0; k < 36; ++k) {
-            const int ra = k / 6, ca = k % 6, fa = pb_fa[pb], fb = pb_fb[pb];
-            int v;
-            if (fa == fb)
-                v = ra >= ca ? ((6 * fa + ca) * ld + 6 * fa + ra) | (ra == ca ? kMfMapLambda : 0) : -1;
-            else
-                v = (6 * fa + ra) * ld + 6 * fb + ca;  // S[6fa+ra][6fb+ca] -> its lower mirror
-            map[36 * pb + k] = v;
-        }
-    for (int i = 0; i < 6 * nf; ++i) map[36 * n_pb + i] = i * ld + np;  // b_i -> row NP, column i
-    for (int i = 0; i < 6 * nf; ++i) map[36 * n_pb + 6 * nf + i] = -2 - i;
-}
-
-// combine_system with the sums scattered straight into M (and g_c into gsh) by the map
-// The partial systems' loads are issued before the LM state's (whose done flag decides whether
-// anything is stored and whose lambda joins the diagonal), so the state's round trip overlaps
-// theirs.  Returns the state's done flag (nothing stored then).
-template <int NF>
-__device__ bool combine_mapped(const Geometry& G, const Prob& Pr, const Work& Wk, double* M, double* gsh,
-                               const LmState* st, int* fail) {
-    constexpr int NE = (NF * (NF + 1) / 2) * 36 + 12 * NF;  // the template's (upper bound)
-    constexpr int T = kK5Threads, kE = (NE + T - 1) / T;
-    const size_t L = sys_len(G);
-    const int ne = G.n_pb * 36 + 12 * G.n_free;  // this window's entries (batched: may be fewer)
-    const int tid = threadIdx.x;
-    double v[kE][kGrp];
-    int dst[kE];
-#pragma unroll
-    for (int i = 0; i < kE; ++i) {  // (branch-free: clamped loads; an entry past ne is never stored)
-        const int e = tid + T * i, ec = min(e, ne - 1);
-        const int d = Pr.dmap[ec];
-        dst[i] = e < ne ? d : -1;
-#pragma unroll
-        for (int x = 0; x < kGrp; ++x) v[i][x] = Wk.cpart[(size_t)x * L + ec];
-    }
-    // then the K4 wave partials (initial cost) and the singular flag, behind them (branch-free:
-    // clamped loads, the ones past the last wave dropped at the sum -- a zeroing select here made
-    // the compiler wait for these loads before issuing the partial systems')
-    double pa[16];
-    int sing = 0;
-    if (tid < 64) {
-        const int wl = max(G.n_wave - 1, 0);
-#pragma unroll
-        for (int k = 0; k < 16; ++k) pa[k] = Wk.partA[min(tid + 64 * k, wl) * kPartA];
-        sing = *Wk.singular;
-    }
-    const int done = st->done;
-    const double lambda = st->lambda;
-    // keep the compiler from sinking the partial systems' loads under the done branch
-#pragma unroll
-    for (int i = 0; i < kE; ++i)
-#pragma unroll
-        for (int x = 0; x < kGrp; ++x) __asm__ volatile("" ::"v"(v[i][x]));
-    if (done) return true;
-#pragma unroll
-    for (int i = 0; i < kE; ++i) {
-        double a = v[i][0];
-#pragma unroll
-        for (int x = 1; x < kGrp; ++x) a += v[i][x];
-        const int d = dst[i];
-        if (d >= 0) {
-            if (d & kMfMapLambda) a += lambda;
-            M[d & (kMfMapLambda - 1)] = a;
-        } else if (d <= -2) {
-            gsh[-2 - d] = a;
-        }
-    }
-    if (tid < 64) {
-        double c = 0.0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) c += tid + 64 * k < G.n_wave ? pa[k] : 0.0;
-        for (int w = tid + 64 * 16; w < G.n_wave; w += 64) c += Wk.partA[w * kPartA];
-        c = wave_sum_det(c);
-        if (tid == 0) {
-            Wk.sys[G.n_pb * 36 + 12 * G.n_free] = c;  // the decision of iteration 0 reads the initial cost here
-            *fail = sing;
-        }
-    }
-    return false;
-}
-
-// combine_p2p's exchange in flag-in-word form (RSVIO_P2P_LL=1, A/B): every entry (and the three
-// scalars: initial cost, singular flag, wave count) goes to every rank as two tagged 8-byte words
-// -- no fence, no flags -- and the reader polls the words themselves, every rank's words of its
-// entries in flight together (ranks in two groups of 4), re-reading until all carry this
-// exchange's tag.  Same sums in the same rank order as the flag protocol: the same bits.
-template <int NF>
-__device__ bool combine_p2p_ll(const Geometry& G, const Work& Wk, double* M, double* gsh, int* fail, const P2P& P,
-                               unsigned long long* xgen, int* err,
-                               const double (&v)[((NF * (NF + 1) / 2) * 36 + 12 * NF + kK5Threads - 1) / kK5Threads][kGrp],
-                               const int (&dst)[((NF * (NF + 1) / 2) * 36 + 12 * NF + kK5Threads - 1) / kK5Threads],
-                               const double (&pa)[16], int sing, double lambda, unsigned long long gen) {
-    constexpr int NE = (NF * (NF + 1) / 2) * 36 + 12 * NF;
-    constexpr int T = kK5Threads, kE = (NE + T - 1) / T;
-    const int ne = G.n_pb * 36 + 12 * G.n_free;
-    const int tid = threadIdx.x, nr = P.nranks, me = P.rank, par = (int)(gen & 1);
-    const unsigned g32 = (unsigned)gen;
-#pragma unroll
-    for (int i = 0; i < kE; ++i) {
-        const int e = tid + T * i;
-        if (e >= ne) break;
-        double a = v[i][0];
-#pragma unroll
-        for (int x = 1; x < kGrp; ++x) a += v[i][x];
-        if (me == 0 && dst[i] >= 0 && (dst[i] & kMfMapLambda)) a += lambda;
-        for (int r = 0; r < nr; ++r) ll_put(p2p_llsys(P.peer[r], par, me) + 2 * (size_t)e, a, g32);
-    }
-    double c = 0.0;
-    if (tid < 64) {
-#pragma unroll
-        for (int k = 0; k < 16; ++k) c += tid + 64 * k < G.n_wave ? pa[k] : 0.0;
-        for (int w = tid + 64 * 16; w < G.n_wave; w += 64) c += Wk.partA[w * kPartA];
-        c = wave_sum_det(c);
-    }
-    // the scalars go last, once every thread's entry stores have completed (vmcnt(0), then the
-    // barrier), so a reader that sees a rank's scalars finds its entries there too: the readers
-    // poll the 6 scalar words of each rank and read the entries once (still tag-checked), instead
-    // of every thread re-reading all its entries' words of every rank until they arrive -- traffic
-    // that, with four ranks on one GPU, starved the last rank's own progress until the spin bound
-    __builtin_amdgcn_s_waitcnt(kWaitStores);
-    __syncthreads();
-    if (tid < nr) {  // lane r pushes the scalars to rank r
-        unsigned long long* d = p2p_llsys(P.peer[tid], par, me) + 2 * (size_t)ne;
-        ll_put(d, c, g32);
-        ll_put(d + 2, sing ? 1.0 : 0.0, g32);
-        ll_put(d + 4, (double)G.n_wave, g32);
-    }
-    const unsigned long long* mine = p2p_llsys(P.peer[me], par, 0);
-    // scalars: lane r of wave 0 reads rank r's three (the sums in rank order by lane 0, below)
-    __shared__ double sc[kP2PMax][3];
-    if (tid < nr) {
-        const unsigned long long* a = mine + (size_t)tid * 2 * kP2PMsg + 2 * (size_t)ne;
-        unsigned long long ws[6];
-        long long spins = 0;
-        for (;;) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) ws[k] = __hip_atomic_load(a + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            bool ok = true;
-#pragma unroll
-            for (int k = 0; k < 6; ++k) ok &= (unsigned)(ws[k] >> 32) == g32;
-            if (ok) break;
-            if (++spins > (1ll << 25)) {
-                atomicExch(err, 1);
-                break;
-            }
-            __builtin_amdgcn_s_sleep(2);
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            sc[tid][k] = __longlong_as_double((long long)((ws[2 * k] & 0xffffffffull) | (ws[2 * k + 1] << 32)));
-    }
-    __syncthreads();
-    // entries: every rank's two words of this thread's entries, ranks in groups of 2 or 4
-    double acc[kE];
-#pragma unroll
-    for (int i = 0; i < kE; ++i) acc[i] = 0.0;
-    const bool late = nr <= 2 ? ll_group_sums<kE, 2>(mine, nr, ne, tid, T, g32, acc)
-                              : ll_group_sums<kE, 4>(mine, nr, ne, tid, T, g32, acc);
-    if (late) atomicExch(err, 1);
-#pragma unroll
-    for (int i = 0; i < kE; ++i) {
-        const int e = tid + T * i;
-        if (e >= ne) break;
-        const int d = dst[i];
-        if (d >= 0)
-            M[d & (kMfMapLambda - 1)] = acc[i];
-        else if (d <= -2)
-            gsh[-2 - d] = acc[i];
-    }
-    if (tid == 0) {
-        double cs = 0.0, f = 0.0;
-        for (int r = 0; r < nr; ++r) {
-            cs += sc[r][0];
-            f += sc[r][1];
-        }
-        Wk.sys[ne] = cs;  // the decision of iteration 0 reads the (all-reduced) initial cost here
-        *fail = f != 0.0;
-        *xgen = gen;
-    }
-    if (tid < nr && P.xnw) P.xnw[tid] = (int)sc[tid][2];
-    return false;
-}
-
-// combine_mapped for the landmark-sharded path over the P2P exchange (X1 folded into K5): this
-// rank's reduced system is summed from its partials as combine_mapped does (+ lambda on rank 0,
-// after the sum, as K4d), each entry pushed from its register into slot [parity][rank] of every
-// peer's exchange buffer together with the rank's initial cost and singular flag; after the
-// system-scope flags of every rank have arrived, each thread sums its entries over the slots in
-// RANK ORDER (identical bits on every rank, and the same bits as X1's exchange into sys followed
-// by K5's read of sys) and scatters them into M / gsh by the map.  Returns the state's done flag:
-// every rank takes the same decision, so either all exchange or none does.  LL: the flag-in-word
-// form (combine_p2p_ll) -- a kernel of its own, so that its polling loops' registers do not
-// inflate the flag protocol's (one kernel holding both took 399 VGPRs, AGPR copies on the
-// prologue's path, +1.3 us per K5 at one rank against the unsharded combine)
-template <int NF, bool LL>
-__device__ bool combine_p2p(const Geometry& G, const Prob& Pr, const Work& Wk, double* M, double* gsh,
-                            const LmState* st, int* fail, const P2P& P, unsigned long long* xgen, int* err) {
-    constexpr int NE = (NF * (NF + 1) / 2) * 36 + 12 * NF;
-    constexpr int T = kK5Threads, kE = (NE + T - 1) / T;
-    const size_t L = sys_len(G);
-    const int ne = G.n_pb * 36 + 12 * G.n_free;
-    const int tid = threadIdx.x, nr = P.nranks, me = P.rank;
-    // the exchange's generation: loaded by every thread (one address), waited for at its first
-    // use after the partial systems' loads are in flight -- not an LDS broadcast by one thread,
-    // whose store made wave 0 wait a whole round trip (with the pose loads ahead of it) before
-    // issuing its share of those loads, and cost a barrier
-    const unsigned long long gen0 = *xgen;
-    double v[kE][kGrp];
-    int dst[kE];
-#pragma unroll
-    for (int i = 0; i < kE; ++i) {  // (branch-free: clamped loads; an entry past ne is never stored)
-        const int e = tid + T * i, ec = min(e, ne - 1);
-        const int d = Pr.dmap[ec];
-        dst[i] = e < ne ? d : -1;
-#pragma unroll
-        for (int x = 0; x < kGrp; ++x) v[i][x] = Wk.cpart[(size_t)x * L + ec];
-    }
-    // then the K4 wave partials (initial cost) and the singular flag, behind them (branch-free:
-    // clamped loads, the ones past the last wave dropped at the sum -- a zeroing select here made
-    // the compiler wait for these loads before issuing the partial systems')
-    double pa[16];
-    int sing = 0;
-    if (tid < 64) {
-        const int wl = max(G.n_wave - 1, 0);
-#pragma unroll
-        for (int k = 0; k < 16; ++k) pa[k] = Wk.partA[min(tid + 64 * k, wl) * kPartA];
-        sing = *Wk.singular;
-    }
-    const int done = st->done;
-    const double lambda = st->lambda;
-#pragma unroll
-    for (int i = 0; i < kE; ++i)
-#pragma unroll
-        for (int x = 0; x < kGrp; ++x) __asm__ volatile("" ::"v"(v[i][x]));
-    if (done) return true;
-    const unsigned long long gen = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)gen0) +
-                                   ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(gen0 >> 32)) << 32) + 1;
-    const int par = (int)(gen & 1);
-    if constexpr (LL) return combine_p2p_ll<NF>(G, Wk, M, gsh, fail, P, xgen, err, v, dst, pa, sing, lambda, gen);
-    // this rank's entries stay in registers (own): only the peers' slots are written, flagged,
-    // waited for and read back (round 5; the own slot's uncached write, flag and re-read were the
-    // exchange's whole cost at one rank)
-    double own[kE];
-#pragma unroll
-    for (int i = 0; i < kE; ++i) {
-        const int e = tid + T * i;
-        double a = v[i][0];
-#pragma unroll
-        for (int x = 1; x < kGrp; ++x) a += v[i][x];
-        if (me == 0 && dst[i] >= 0 && (dst[i] & kMfMapLambda)) a += lambda;
-        own[i] = a;
-        if (e < ne)
-            for (int r = 0; r < nr; ++r)
-                if (r != me) p2p_slot(P.peer[r], par, me)[e] = a;
-    }
-    __shared__ double osc[2];  // this rank's initial cost and singular flag
-    if (tid < 64) {
-        double c = 0.0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) c += tid + 64 * k < G.n_wave ? pa[k] : 0.0;
-        for (int w = tid + 64 * 16; w < G.n_wave; w += 64) c += Wk.partA[w * kPartA];
-        c = wave_sum_det(c);
-        if (tid == 0) {
-            osc[0] = c;
-            osc[1] = sing ? 1.0 : 0.0;
-        }
-        if (tid < nr && tid != me) {  // lane r pushes the scalars to rank r
-            double* d = p2p_slot(P.peer[tid], par, me);
-            d[ne] = c;
-            d[ne + 1] = sing ? 1.0 : 0.0;
-            d[ne + 2] = (double)G.n_wave;  // (per rank, not summed: the folded trial exchange's bound)
-        }
-    }
-    if (nr > 1) __threadfence_system();
-    __syncthreads();
-    if (tid < nr && tid != me)
-        __hip_atomic_store(p2p_flags(P.peer[tid]) + par * kP2PMax + me, gen, __ATOMIC_RELEASE,
-                           __HIP_MEMORY_SCOPE_SYSTEM);
-    if (tid < nr && tid != me) {
-        const unsigned long long* f = p2p_flags(P.peer[me]) + par * kP2PMax + tid;
-        long long spins = 0;
-        while (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) < gen) {
-            __builtin_amdgcn_s_sleep(2);
-            if (++spins > (1ll << 25)) {  // a peer never arrived: report, do not hang
-                atomicExch(err, 1);
-                break;
-            }
-        }
-        // relaxed polls (no L2 invalidate per poll), one acquire once the flag is seen
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-    }
-    __syncthreads();
-    const double* mine = p2p_slot(P.peer[me], par, 0);
-    // this thread's values from a group of ranks in flight together (own from registers, peers'
-    // from their slots), groups in rank order: one round trip per group of 2 (two ranks), 4 (three
-    // or four) or 8 ranks, then the rank-ordered sums
-    double sums[kE];
-#pragma unroll
-    for (int i = 0; i < kE; ++i) sums[i] = 0.0;
-    if (nr <= 2)
-        p2p_group_sums_own<kE, 2>(mine, nr, me, ne, tid, T, own, sums);
-    else if (nr <= 4)
-        p2p_group_sums_own<kE, 4>(mine, nr, me, ne, tid, T, own, sums);
-    else  // 5..8 ranks: every peer's slot in flight together -- one round trip, not two groups of 4
-        p2p_group_sums_own<kE, 8>(mine, nr, me, ne, tid, T, own, sums);
-#pragma unroll
-    for (int i = 0; i < kE; ++i) {
-        const int e = tid + T * i;
-        if (e >= ne) break;
-        const double a = sums[i];
-        const int d = dst[i];
-        if (d >= 0)
-            M[d & (kMfMapLambda - 1)] = a;
-        else if (d <= -2)
-            gsh[-2 - d] = a;
-    }
-    if (tid == 0) {
-        // every peer's two scalars in flight together (unrolled over the rank bound), then the
-        // rank-ordered sums with this rank's own values substituted
-        double cv[kP2PMax], fv[kP2PMax];
-#pragma unroll
-        for (int r = 0; r < kP2PMax; ++r) {
-            const bool peer = r < nr && r != me;
-            cv[r] = peer ? __hip_atomic_load(mine + (size_t)r * kP2PMsg + ne, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)
-                         : osc[0];
-            fv[r] = peer ? __hip_atomic_load(mine + (size_t)r * kP2PMsg + ne + 1, __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_SYSTEM)
-                         : osc[1];
-        }
-        double c = 0.0, f = 0.0;
-#pragma unroll
-        for (int r = 0; r < kP2PMax; ++r)
-            if (r < nr) {
-                c += cv[r];
-                f += fv[r];
-            }
-        Wk.sys[ne] = c;  // the decision of iteration 0 reads the (all-reduced) initial cost here
-        *fail = f != 0.0;
-        *xgen = gen;
-    }
-    if (tid < nr && P.xnw)
-        P.xnw[tid] = tid == me ? G.n_wave
-                               : (int)__hip_atomic_load(mine + (size_t)tid * kP2PMsg + ne + 2, __ATOMIC_RELAXED,
-                                                        __HIP_MEMORY_SCOPE_SYSTEM);
-    return false;
-}
-
-// pivot J of panel H (width PW) by wave 0: inv = 1 / d_K ready.  Column J+1 (the next pivot's)
-// and column J+2 are updated from readlanes of the unscaled column u; columns >= J+3 from values
-// of u read this step and consumed one step later (uq, with the pivot's l as lp) -- by readlane
-// since round 6 (LDS broadcasts before: their wait sat between two pivots' chains).
-template <int H, int J, int PW, bool KD = false>
-__device__ __forceinline__ void mf_pivot(double (&a)[kMfPanel], double (&uq)[kMfPanel], double lp, double inv,
-                                         double* Lf, double* Up, int lane, bool& bad, double* Dv = nullptr) {
-    constexpr int K = kMfPanel * H + J;
-    const double u = a[J];
-    if constexpr (KD)  // 1 / d_K kept (the covariance inverts the factor)
-        if (lane == 0) Dv[K] = inv;
-    double inv_next = 1.0;
-    double uk1 = 0.0;
-    if constexpr (J + 1 < PW) {
-        // the next pivot on the shortest chain: d_{K+1} = a_{K+1,K+1} - u_{K+1,K}^2 / d_K, with
-        // u_{K+1,K} and a_{K+1,K+1} read before 1/d_K is known -- inv -> fma -> rcp (+ Newton),
-        // uniform on every lane, no readlane on the chain
-        uk1 = rl64(u, K + 1);
-        const double piv = fma(-(uk1 * uk1), inv, rl64(a[J + 1], K + 1));
-        bad |= !(piv > 0.0) || !isfinite(piv);
-#ifndef RSVIO_K5_RCP_LATE
-        // the hardware reciprocal issued here, before the barrier (round 6): left to the
-        // compiler, IR code sinking moved it past this pivot's other updates, so ~12 issue slots
-        // sat between the pivot and its reciprocal on the 1/d chain; the Newton steps follow where
-        // the next pivot needs them (rcp_f64's operations, the same bits).  Measured neutral
-        // (0.0302-0.0304 ms per LM iteration either way, profiles/r06i_rcp_ab.txt): the chain's
-        // issue slots, not this placement, bound it
-        double y0 = __builtin_amdgcn_rcp(piv);
-        __asm__ volatile("" : "+v"(y0));
-        const double e = fma(-piv, y0, 1.0);
-        inv_next = fma(y0, fma(e, e, e), y0);
-#else
-        inv_next = rcp_f64(piv);
-#endif
-    }
-    const double l = u * inv;
-    if constexpr (J + 1 < PW) a[J + 1] = fma(-l, uk1, a[J + 1]);
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (J > 0)
-#pragma unroll
-        for (int jj = J + 2; jj < PW; ++jj) a[jj] = fma(-lp, uq[jj], a[jj]);
-    if constexpr (J + 2 < PW) a[J + 2] = fma(-l, rl64(u, K + 2), a[J + 2]);
-    Lf[K * kMfLd + lane] = l;  // column K of L (rows > K; row NP: z_K); the upper part is never read
-    Up[J * kMfLd + lane] = u;  // column J of the panel's U = D L
-#ifndef RSVIO_K5_LDSQ
-    // round 6: the later columns' multipliers by readlane too -- no LDS read and no wait on it
-    // between this pivot's chain and the next (0.0305 -> 0.0302 ms per LM iteration, 3 of 3 A/B
-    // pairs, profiles/r06h_rlq_ab.txt); -DRSVIO_K5_LDSQ: LDS broadcasts (round 3-5)
-#pragma unroll
-    for (int jj = J + 3; jj < PW; ++jj) uq[jj] = rl64(u, kMfPanel * H + jj);
-#else
-#pragma unroll
-    for (int jj = J + 3; jj < PW; ++jj) uq[jj] = Up[J * kMfLd + kMfPanel * H + jj];  // broadcasts
-#endif
-    if constexpr (J + 1 < PW) mf_pivot<H, J + 1, PW, KD>(a, uq, l, inv_next, Lf, Up, lane, bad, Dv);
-}
-
-// Panel H (columns 8H .. 8H + PW - 1) factored by wave 0 from M into Lf and its U buffer Uh.
-template <int NF, int H, bool KD = false>
-__device__ __forceinline__ void mf_factor(const double* M, double* Lf, double* Uh, int lane, bool& bad,
-                                          double* Dv = nullptr) {
-    constexpr int NP = MfDims<NF>::NP;
-    constexpr int C0 = kMfPanel * H;
-    constexpr int PW = (NP - C0) < kMfPanel ? (NP - C0) : kMfPanel;
-    double a[kMfPanel], uq[kMfPanel];
-#pragma unroll
-    for (int jj = 0; jj < kMfPanel; ++jj) {
-        a[jj] = jj < PW ? M[(C0 + jj) * kMfLd + lane] : 0.0;
-        uq[jj] = 0.0;
-    }
-    const double piv = rl64(a[0], C0);
-    bad |= !(piv > 0.0) || !isfinite(piv);
-    mf_pivot<H, 0, PW, KD>(a, uq, 0.0, rcp_f64(piv), Lf, Uh, lane, bad, Dv);
-}
-
-// The trailing update of panel H on the matrix cores: lower tiles (I, J), I >= J, of tile columns
-// J0 <= J < J1, C_IJ += (-U_I) L_J^T over the panel's 8 columns (2 MFMAs per tile), tile t of the
-// flattened list taken by wave `wid` of `nw`.  A tile holding factored columns gets garbage there
-// (their L lives in Lf).
-template <int NF, int H>
-__device__ __forceinline__ void mf_update(double* M, const double* Lf, const double* Uh, int lane, int wid, int nw,
-                                          int J0, int J1) {
-    constexpr int NT = MfDims<NF>::NT;
-    constexpr int C0 = kMfPanel * H;
-    const int i16 = lane & 15, k4 = lane >> 4;
-    int ntile = 0;
-    for (int J = J0; J < J1; ++J) ntile += NT - J;
-    for (int t = wid; t < ntile; t += nw) {
-        int TJ = J0, rem = t;
-        while (rem >= NT - TJ) {
-            rem -= NT - TJ;
-            ++TJ;
-        }
-        const int TI = TJ + rem;
-        double av[2], bv[2];
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            const int kk = 4 * m + k4;
-            av[m] = -Uh[kk * kMfLd + 16 * TI + i16];
-            bv[m] = Lf[(C0 + kk) * kMfLd + 16 * TJ + i16];
-        }
-        mf_dbl4 c;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) c[r] = M[(16 * TJ + i16) * kMfLd + 16 * TI + k4 + 4 * r];
-        c = __builtin_amdgcn_mfma_f64_16x16x4f64(av[0], bv[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f64_16x16x4f64(av[1], bv[1], c, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) M[(16 * TJ + i16) * kMfLd + 16 * TI + k4 + 4 * r] = c[r];
-    }
-}
-
-// Panel H is factored (Lf, Up[H & 1]) and visible to every wave.  Look-ahead: wave 0 updates the
-// tile column T0 that holds panel H + 1's columns and factors panel H + 1 straight away (into the
-// other U buffer), while waves 1-3 update the tile columns past T0 -- disjoint columns of M, so
-// the next pivot chain starts without waiting for the rest of the trailing update.
-template <int NF, int H, bool KD = false>
-__device__ __forceinline__ void mf_panel(double* M, double* Lf, double* Up, int tid, bool& bad, double* Dv = nullptr) {
-    constexpr int NT = MfDims<NF>::NT, NH = MfDims<NF>::NH;
-    constexpr int C0 = kMfPanel * H;
-    const int lane = tid & 63, wave = tid >> 6;
-    if constexpr (H == 0) STAMP(9); else if constexpr (H == 2) STAMP(15); else if constexpr (H == 4) STAMP(30);
-    if constexpr (H + 1 == NH) STAMP(7);
-    if constexpr (H + 1 < NH) {
-        constexpr int T0 = (C0 + kMfPanel) / 16;  // the tile column of panel H + 1
-        double* Uh = Up + (H & 1) * kMfPanel * kMfLd;
-        if (wave == 0) {
-            mf_update<NF, H>(M, Lf, Uh, lane, 0, 1, T0, T0 + 1);
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");  // the column's updates before its reads
-            __builtin_amdgcn_wave_barrier();
-            mf_factor<NF, H + 1, KD>(M, Lf, Up + ((H + 1) & 1) * kMfPanel * kMfLd, lane, bad, Dv);
-        } else {
-            mf_update<NF, H>(M, Lf, Uh, lane, wave - 1, kK5Threads / 64 - 1, T0 + 1, NT);
-        }
-        __syncthreads();
-        if constexpr (H == 0) STAMP(13); else if constexpr (H == 2) STAMP(19); else if constexpr (H == 4) STAMP(31);
-        mf_panel<NF, H + 1, KD>(M, Lf, Up, tid, bad, Dv);
-    }
-}
+#include "ba_k5_panel.hpp"  // K5 on the matrix cores, 8-column panels (<= 10 free keyframes)
 
 // ---------------------------------------------------------------------------------------
 // K5 by 6x6 block pivots (round 5): the solver of 11..20 free keyframes (camera_solve_blk_body);
-// for <= 10 the 8-column panels above stay the default (measured faster at config 3, 12.7 vs
-// 13.9 us) and -DRSVIO_K5_BLOCK builds this one there (A/B).  The camera system's own blocks:
-// step k factors keyframe k's diagonal block as a whole.
+// for <= 10 the 8-column panels above stay (measured faster at config 3, 12.7 vs 13.9 us; the
+// build-time switch that put this one there for the A/B is gone).  The camera system's own
+// blocks: step k factors keyframe k's diagonal block as a whole.
 //   * Chain wave (wave 0, lane = row; rows lane and lane + 64 past 64 rows): it holds column
 //     block k of its rows in registers, fully updated.  The diagonal block's 21 lower entries go
 //     to every lane through LDS (one store by its 6 rows, one broadcast read), and every lane
@@ -2375,6 +1859,10 @@ __device__ __forceinline__ void mf_panel(double* M, double* Lf, double* Up, int 
     do {             \
     } while (0)
 #endif
+
+constexpr int kBkLd = 129;  // kMfLd's counterpart past 10 free keyframes (up to 121 rows; odd)
+// the block solver's instantiations past 10 free keyframes (a window pads up to the next one)
+inline int bk_template_nf(int n_free) { return n_free <= 13 ? 13 : n_free <= 16 ? 16 : 20; }
 
 template <int NF>
 struct BkDims {
@@ -2454,8 +1942,8 @@ __device__ __forceinline__ void bk_update(double* M, const double* Uk, int lane,
 }
 
 // Block step K.  a: column block K of the chain wave's rows (updated); U: 2 x 6 x LD doubles
-// (blocks alternate); Dsc / Lsc: 36 doubles each of chain-wave scratch.  Every wave of the block
-// runs every step (one barrier each).
+// (blocks alternate); Lsc: 36 doubles of chain-wave scratch (Dsc: 36 more, unused since the diagonal
+// block goes by readlane).  Every wave of the block runs every step (one barrier each).
 template <int NF, int K, int NW, bool KD = false>
 __device__ __forceinline__ void bk_steps(double* M, double* U, double* Dsc, double* Lsc,
                                          double (&a)[BkDims<NF>::RPL][6], int tid, bool& bad,
@@ -2470,29 +1958,13 @@ __device__ __forceinline__ void bk_steps(double* M, double* U, double* Dsc, doub
     WSTAMP(7, 160 + K);                      // slots 160..179: wave 7 (the last update wave) the same
     if (wave == 0) {
         double Dg[6][6], Lg[6][6], inv[6];
-#ifdef RSVIO_BK_DIAG_LDS
-        // the diagonal block to every lane: its 6 rows store, every lane reads the lower 21
-#pragma unroll
-        for (int h = 0; h < RPL; ++h) {
-            const int i = lane + 64 * h - c0;
-            if (i >= 0 && i < 6)
-#pragma unroll
-                for (int j = 0; j < 6; ++j) Dsc[6 * i + j] = a[h][j];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int i = 0; i < 6; ++i)
-#pragma unroll
-            for (int j = 0; j <= i; ++j) Dg[i][j] = Dsc[6 * i + j];
-#else
         // the diagonal block to every lane by readlane: row c0 + i is lane (c0 + i) % 64's register
         // set (c0 + i) / 64, both compile-time -- no LDS store, wave barrier and read on the chain
+        // (as it went through Dsc before: its 6 rows stored, every lane read the lower 21)
 #pragma unroll
         for (int i = 0; i < 6; ++i)
 #pragma unroll
             for (int j = 0; j <= i; ++j) Dg[i][j] = rl64(a[(c0 + i) >> 6][j], (c0 + i) & 63);
-#endif
         // its LDL^T, redundantly on every lane: Dg[i][j] (i > j) ends as U = (D L)[i][j], Lg = L
 #pragma unroll
         for (int j = 0; j < 6; ++j) {
@@ -2594,126 +2066,6 @@ __device__ __forceinline__ void bk_factor(double* M, double* U, double* S, int t
         }
     }
     bk_steps<NF, 0, NW, KD>(M, U, S, S + 36, a, tid, bad, env, Dv);
-}
-
-template <int NF, bool LL = false>
-__device__ void camera_solve_mfma_body(const Geometry& G, const Prob& Pr, const Work& Wk, int combine,
-                                       const P2P* P = nullptr, unsigned long long* xgen = nullptr, int* err = nullptr) {
-    static_assert(NF >= 1 && NF <= 10, "one row per lane: n <= 60");
-    constexpr int NP = MfDims<NF>::NP, NPP = MfDims<NF>::NPP;
-    __shared__ __attribute__((aligned(16))) double M[NPP * kMfLd];
-    __shared__ __attribute__((aligned(16))) double Lf[NPP * kMfLd];
-    __shared__ __attribute__((aligned(16))) double Up[2 * kMfPanel * kMfLd];  // U of panels H & 1
-    __shared__ double gsh[NP];
-    __shared__ int fail;
-    RTSTAMP(4);
-    LmState* st = Wk.st;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nF = G.n_free, n = 6 * nF;
-    const int SC0 = G.n_pb * 36 + 12 * nF;
-    // both pose buffers (the state's cur picks one), loaded with the partial systems, before the
-    // state itself
-    double p7b[2][7];
-    int fidx = -1;
-    if (wave == 0 && lane < G.n_kf) {
-        fidx = Pr.free_idx[lane];
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int i = 0; i < 7; ++i) p7b[b][i] = Wk.pose[b][7 * lane + i];
-    } else {
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int i = 0; i < 7; ++i) p7b[b][i] = i == 3 ? 1.0 : 0.0;
-    }
-    STAMP(0);
-    if (combine == 2) {  // sharded over P2P: this rank's system exchanged in the prologue (X1 folded in)
-        if (combine_p2p<NF, LL>(G, Pr, Wk, M, gsh, st, &fail, *P, xgen, err)) return;
-    } else if (combine) {
-        if (combine_mapped<NF>(G, Pr, Wk, M, gsh, st, &fail)) return;
-    } else {  // sharded: the all-reduced system (+ lambda on the owner rank) from sys, by the map
-        if (st->done) return;
-        const double* sys = Wk.sys;
-        const int ne = G.n_pb * 36 + 12 * nF;
-        for (int e = tid; e < ne; e += kK5Threads) {
-            const int d = Pr.dmap[e];
-            if (d >= 0)
-                M[d & (kMfMapLambda - 1)] = sys[e];
-            else if (d <= -2)
-                gsh[-2 - d] = sys[e];
-        }
-        if (tid == 0) fail = sys[SC0 + 1] != 0.0;
-    }
-    const int cur = st->cur;
-    double p7[7];
-#pragma unroll
-    for (int i = 0; i < 7; ++i) p7[i] = cur ? p7b[1][i] : p7b[0][i];
-    if (n < NP) {
-        // a window with fewer free keyframes than the template (batched mode): its rows and
-        // columns [n, NP) are identity padding, and the b row is zero there
-        for (int e = tid; e < NP * (NP + 1); e += kK5Threads) {
-            const int c = e / (NP + 1), r = e - c * (NP + 1);
-            if (r >= c && ((r >= n && r < NP) || (c >= n && c < NP))) M[c * kMfLd + r] = r == c ? 1.0 : 0.0;
-        }
-    }
-    __syncthreads();
-    STAMP(1);
-    // the singular flag of this iteration's K4c is already in fail (combine_mapped / combine_p2p
-    // load it with the partial systems; the sys path's K4d / X1 carried it and cleared it): only
-    // its reset for the next iteration here (re-reading it cost a round trip on the chain)
-    if (tid == 0) *Wk.singular = 0;
-    const double gcl_v = (wave == 0 && lane < n) ? gsh[lane] : 0.0;
-    __syncthreads();
-    STAMP(2);
-    if (fail) {
-        if (tid == 0) k5_result(st, 0, 0.0, 0.0);
-        return;
-    }
-    bool bad = false;
-#ifndef RSVIO_K5_BLOCK
-    if (wave == 0) mf_factor<NF, 0>(M, Lf, Up, lane, bad);
-    __syncthreads();
-    mf_panel<NF, 0>(M, Lf, Up, tid, bad);
-    double* const Lres = Lf;
-#else
-    static_assert(BkDims<NF>::NPP == NPP && BkDims<NF>::LD == kMfLd, "one M layout for both factorisations");
-    bk_factor<NF, kK5Threads / 64>(M, Up, Lf, tid, bad, G.env);
-    double* const Lres = M;  // L in place in M's columns
-#endif
-    if (wave != 0) return;
-    if (bad) {
-        if (lane == 0) k5_result(st, 0, 0.0, 0.0);
-        return;
-    }
-    // z_j = L[NP][j] (row NP of the eliminated augmented matrix); L^T x = z (unit diagonal):
-    // lane j, L[i][j] = Lf[j][i] column-major, zero for i <= j so the update needs no select
-    const int lj = lane < NP ? lane : 0;
-    double yv = lane < NP ? Lres[lj * kMfLd + NP] : 0.0;
-    double lt[NP];
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        const double m = Lres[lj * kMfLd + j];
-        lt[j] = lane < j ? m : 0.0;
-    }
-#pragma unroll
-    for (int j = NP - 1; j >= 0; --j) yv = fma(-lt[j], rl64(yv, j), yv);
-    STAMP(3);
-    k5_finish<NF>(G, Wk, Up, lane < n ? yv : 0.0, gcl_v, n, lane, p7, fidx);
-    RTSTAMP(5);
-}
-
-template <int NF>
-__global__ __launch_bounds__(kK5Threads) void ba_camera_solve_mfma(Geometry G, Prob Pr, Work Wk, int combine) {
-    camera_solve_mfma_body<NF>(G, Pr, Wk, combine);
-}
-
-// K5 of the landmark-sharded iteration over the P2P exchange: the exchange of the reduced system
-// (X1: combine + push + flags + rank-ordered sum) in the prologue, then the same factorisation
-template <int NF, bool LL>
-__global__ __launch_bounds__(kK5Threads) void ba_camera_solve_mfma_p2p(Geometry G, Prob Pr, Work Wk, P2P P,
-                                                                        unsigned long long* xgen, int* err) {
-    camera_solve_mfma_body<NF, LL>(G, Pr, Wk, 2, &P, xgen, err);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2955,289 +2307,7 @@ __global__ __launch_bounds__(64 * kBkWaves) void ba_camera_solve_blk(Geometry G,
     camera_solve_blk_body<NF>(G, Pr, Wk, combine);
 }
 
-// ---------------------------------------------------------------------------------------
-// K5 for 11..20 free keyframes (61 <= n <= 120): the pipelined register LDL^T with two rows per
-// lane (rows lane and lane + 64) over 8 waves.  The system is padded to NP = 6 NF (NF in
-// {13, 16, 20}) with identity rows / columns after the real ones and b as row NP: a padded
-// column has pivot 1 and zero couplings, so every real entry sees exactly the operations of
-// the unpadded factorisation.  Wave WV owns columns [WV CW, WV CW + CW); a wave whose columns
-// all lie at or past 64 skips the upper half of the rows (lower triangle only).  LDS keeps the
-// unscaled columns U[.][K] = (D L)[.][K] and 1/d_K; L = U / d is re-formed with the owner's
-// multiply (same bits), so one NP x 121 array serves the updates and the back substitution.
-// ---------------------------------------------------------------------------------------
-constexpr int kX2Waves = 8;
-constexpr int kUcLd = kMaxN + 1;  // 121 (odd)
-
-__device__ __forceinline__ const double* sys_lower_rt(const double* sys, int nf, int r, int c) {
-    const int n = 6 * nf;
-    if (r == n) return sys + (nf * (nf + 1) / 2) * 36 + c;
-    const int a = c / 6, b = r / 6;
-    const int pb = a * nf - a * (a - 1) / 2 + (b - a);
-    const int k = (a == b) ? (r % 6) * 6 + (c % 6) : (c % 6) * 6 + (r % 6);
-    return sys + pb * 36 + k;
-}
-
-template <int NP, int CW, int WV, int K>
-__device__ __forceinline__ void chol2_step(double (&a)[2][CW], int lane, double* Uc, double* dinv, double* sink,
-                                           int* progress, int& seen, bool& bad, double inv) {
-    constexpr int c0 = WV * CW;
-    constexpr int c1 = (c0 + CW < NP) ? c0 + CW : NP;
-    constexpr int Q0 = (c0 < 64) ? 0 : 1;             // first active half of the rows
-    constexpr int KN = (K + 1 < c0) ? K + 2 : K + 1;  // consume columns in pairs
-    if constexpr (K < c0) {
-        if (seen < KN) {
-            do {
-                seen = __hip_atomic_load(progress, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (seen >= KN) break;
-                __builtin_amdgcn_s_sleep(1);
-            } while (true);
-        }
-        const double* u = Uc + K * kUcLd;
-        const double di = dinv[K];
-        double lr[2];
-#pragma unroll
-        for (int q = Q0; q < 2; ++q) lr[q] = u[min(lane + 64 * q, NP)] * di;
-        if constexpr (KN == K + 2) {
-            const double* u2 = Uc + (K + 1) * kUcLd;
-            const double di2 = dinv[K + 1];
-            double lr2[2];
-#pragma unroll
-            for (int q = Q0; q < 2; ++q) lr2[q] = u2[min(lane + 64 * q, NP)] * di2;
-            double v1[CW], v2[CW];
-#pragma unroll
-            for (int jj = 0; jj < CW; ++jj) {
-                v1[jj] = u[c0 + jj];
-                v2[jj] = u2[c0 + jj];
-            }
-#pragma unroll
-            for (int q = Q0; q < 2; ++q)
-#pragma unroll
-                for (int jj = 0; jj < CW; ++jj)
-                    if (c0 + jj < NP) a[q][jj] = fma(-lr2[q], v2[jj], fma(-lr[q], v1[jj], a[q][jj]));
-        } else {
-#pragma unroll
-            for (int q = Q0; q < 2; ++q)
-#pragma unroll
-                for (int jj = 0; jj < CW; ++jj)
-                    if (c0 + jj < NP) a[q][jj] = fma(-lr[q], u[c0 + jj], a[q][jj]);
-        }
-        if constexpr (KN == c0) {  // first own pivot
-            const double piv = rl64(a[c0 >> 6][0], c0 & 63);
-            bad |= !(piv > 0.0) || !isfinite(piv);
-            inv = rcp_f64(piv);
-        }
-    } else if constexpr (K < c1) {
-        constexpr int j = K - c0;
-        if constexpr (K > c0) __hip_atomic_store(progress, K, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        double uk[2], l[2];
-#pragma unroll
-        for (int q = Q0; q < 2; ++q) {
-            uk[q] = a[q][j];
-            l[q] = uk[q] * inv;
-            a[q][j] = l[q];
-            // every lane stores (rows past NP into the sink): the release below is then ordered
-            // after each lane's own writes (a lane-divergent store could be scheduled after
-            // another lane's release)
-            double* dst = (q == 0 || lane + 64 <= NP) ? Uc + K * kUcLd + lane + 64 * q : sink + lane;
-            *dst = uk[q];
-        }
-        dinv[K] = inv;  // uniform value, written by every lane for the same reason
-        double piv = 1.0;
-        if constexpr (j + 1 < CW && K + 1 < NP) {
-            constexpr int qn = (K + 1) >> 6, ln = (K + 1) & 63;
-            const double ukn = rl64(uk[qn], ln);
-#pragma unroll
-            for (int q = Q0; q < 2; ++q) a[q][j + 1] = fma(-l[q], ukn, a[q][j + 1]);
-            piv = rl64(a[qn][j + 1], ln);
-        }
-#pragma unroll
-        for (int jj = j + 2; jj < CW; ++jj) {
-            if (c0 + jj < NP) {
-                const double v = rl64(uk[(c0 + jj) >> 6], (c0 + jj) & 63);  // U[c0 + jj][K] from its lane
-#pragma unroll
-                for (int q = Q0; q < 2; ++q) a[q][jj] = fma(-l[q], v, a[q][jj]);
-            }
-        }
-        if constexpr (j + 1 < CW && K + 1 < NP) {
-            bad |= !(piv > 0.0) || !isfinite(piv);
-            inv = rcp_f64(piv);
-        }
-        if constexpr (K + 1 == c1) __hip_atomic_store(progress, K + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    if constexpr (K < c0) {
-#pragma unroll
-        for (int q = Q0; q < 2; ++q)
-#pragma unroll
-            for (int jj = 0; jj < CW; ++jj) __asm__ volatile("" : "+v"(a[q][jj]));
-    }
-    constexpr int KNEXT = (K < c0) ? KN : K + 1;
-    if constexpr (KNEXT < c1) chol2_step<NP, CW, WV, KNEXT>(a, lane, Uc, dinv, sink, progress, seen, bad, inv);
-}
-
-template <int NP, int CW, int WV>
-__device__ __forceinline__ void chol2_pipe(const double* sys, int nf, double* Uc, double* dinv, double* sink, int* progress,
-                                           int* badw, int lane) {
-    constexpr int c0 = WV * CW;
-    constexpr int Q0 = (c0 < 64) ? 0 : 1;
-    const int n = 6 * nf;
-    double a[2][CW];
-    // this wave's columns of its rows straight from sys: real rows / columns from the packed
-    // system, padded ones identity, row NP = b (zero in padded columns), upper triangle zero
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int r = lane + 64 * q;
-#pragma unroll
-        for (int jj = 0; jj < CW; ++jj) {
-            const int c = c0 + jj;
-            double v = 0.0;
-            if (q >= Q0 && c < NP && r <= NP && (c <= r || r == NP)) {
-                if (r == NP) v = c < n ? *sys_lower_rt(sys, nf, n, c) : 0.0;
-                else if (r < n) v = *sys_lower_rt(sys, nf, r, c);
-                else v = (r == c) ? 1.0 : 0.0;
-            }
-            a[q][jj] = v;
-        }
-    }
-    bool bad = false;
-    if constexpr (c0 < NP) {
-        double inv = 0.0;
-        if constexpr (c0 == 0) {
-            const double piv = rl64(a[0][0], 0);
-            bad = !(piv > 0.0) || !isfinite(piv);
-            inv = rcp_f64(piv);
-        }
-        int seen = 0;
-        chol2_step<NP, CW, WV, 0>(a, lane, Uc, dinv, sink + 64 * WV, progress, seen, bad, inv);
-    }
-    if (lane == 0) badw[WV] = bad ? 1 : 0;
-}
-
-template <int NF>
-__global__ __launch_bounds__(64 * kX2Waves) void ba_camera_solve_x2(Geometry G, Prob Pr, Work Wk, int combine) {
-    constexpr int NP = 6 * NF, CW = (NP + kX2Waves - 1) / kX2Waves;
-    static_assert(NP <= kMaxN && NP + 1 <= kUcLd && NP < 128, "padded system too large");
-    __shared__ double Uc[NP * kUcLd];
-    __shared__ double dinv[NP];
-    __shared__ double dcs[128];
-    __shared__ double sink[64 * kX2Waves];  // stores of rows past NP (see chol2_step)
-    __shared__ int badw[kX2Waves];
-    __shared__ int progress;
-    __shared__ int fail;
-    LmState* st = Wk.st;
-    if (st->done) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nF = G.n_free, n = 6 * nF;
-    const double* sys = Wk.sys;
-    const int SG0 = G.n_pb * 36 + 6 * nF, SC0 = SG0 + 6 * nF;
-    const int cur = st->cur;
-    double p7[7] = {0, 0, 0, 1, 0, 0, 0};
-    int fidx = -1;
-    double gcl[2] = {0.0, 0.0};
-    if (wave == 0 && lane < G.n_kf) {
-        fidx = Pr.free_idx[lane];
-#pragma unroll
-        for (int i = 0; i < 7; ++i) p7[i] = Wk.pose[cur][7 * lane + i];
-    }
-    if (combine) {  // single rank: the reduced system from K4c's chunk partials into sys
-        combine_system<64 * kX2Waves>(G, Pr, Wk, Wk.sys, st->lambda, true);
-        __builtin_amdgcn_s_waitcnt(0);
-        __syncthreads();
-    }
-    if (wave == 0)
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-            if (lane + 64 * q < n) gcl[q] = sys[SG0 + lane + 64 * q];
-    if (tid == 0) {
-        fail = (sys[SC0 + 1] != 0.0 || *Wk.singular) ? 1 : 0;
-        *Wk.singular = 0;
-        progress = 0;
-    }
-    __syncthreads();
-    if (fail) {
-        if (tid == 0) k5_result(st, 0, 0.0, 0.0);
-        return;
-    }
-    switch (wave) {
-        case 0: chol2_pipe<NP, CW, 0>(sys, nF, Uc, dinv, sink, &progress, badw, lane); break;
-        case 1: chol2_pipe<NP, CW, 1>(sys, nF, Uc, dinv, sink, &progress, badw, lane); break;
-        case 2: chol2_pipe<NP, CW, 2>(sys, nF, Uc, dinv, sink, &progress, badw, lane); break;
-        case 3: chol2_pipe<NP, CW, 3>(sys, nF, Uc, dinv, sink, &progress, badw, lane); break;
-        case 4: chol2_pipe<NP, CW, 4>(sys, nF, Uc, dinv, sink, &progress, badw, lane); break;
-        case 5: chol2_pipe<NP, CW, 5>(sys, nF, Uc, dinv, sink, &progress, badw, lane); break;
-        case 6: chol2_pipe<NP, CW, 6>(sys, nF, Uc, dinv, sink, &progress, badw, lane); break;
-        default: chol2_pipe<NP, CW, 7>(sys, nF, Uc, dinv, sink, &progress, badw, lane); break;
-    }
-    __syncthreads();
-    if (wave != 0) return;
-    bool anybad = false;
-#pragma unroll
-    for (int w = 0; w < kX2Waves; ++w) anybad |= badw[w] != 0;
-    if (anybad) {
-        if (lane == 0) k5_result(st, 0, 0.0, 0.0);
-        return;
-    }
-    // L^T x = z (unit diagonal), z = row NP of the factor: lane holds rows i = lane, lane + 64;
-    // L[j][i] = U[j][i] / d_i by the owner's multiply.  Padded rows have z = 0: start at n - 1.
-    double yv[2], di[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int i = min(lane + 64 * q, NP - 1);
-        di[q] = dinv[i];
-        yv[q] = Uc[i * kUcLd + NP] * di[q];
-    }
-    constexpr int kBs = 8;
-    for (int j0 = n - 1; j0 >= 0; j0 -= kBs) {
-        double lt[kBs][2];
-#pragma unroll
-        for (int t = 0; t < kBs; ++t) {
-            const int j = max(j0 - t, 0);
-#pragma unroll
-            for (int q = 0; q < 2; ++q) lt[t][q] = Uc[min(lane + 64 * q, NP - 1) * kUcLd + j];
-        }
-#pragma unroll
-        for (int t = 0; t < kBs; ++t) {
-            const int j = j0 - t;
-            if (j < 0) break;
-            const double xj = j >= 64 ? rl64(yv[1], j - 64) : rl64(yv[0], j);
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const double l = lt[t][q] * di[q];
-                const double upd = fma(-l, xj, yv[q]);
-                yv[q] = lane + 64 * q < j ? upd : yv[q];
-            }
-        }
-    }
-    STAMP(4);
-    double x[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) x[q] = lane + 64 * q < n ? yv[q] : 0.0;
-    const double d2 = wave_sum_det(x[0] * x[0] + x[1] * x[1]);
-    const double gd = wave_sum_det(gcl[0] * x[0] + gcl[1] * x[1]);
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int i = lane + 64 * q;
-        if (i < n) {
-            Wk.dc[i] = x[q];
-            dcs[i] = x[q];
-        }
-    }
-    __builtin_amdgcn_s_waitcnt(0xc07f);  // the LDS copy (not the dc store's acknowledgement)
-    __builtin_amdgcn_wave_barrier();
-    if (lane < G.n_kf) {
-        double* qd = Wk.pose[1 - st->cur] + 7 * lane;
-        if (fidx < 0) {
-#pragma unroll
-            for (int i = 0; i < 7; ++i) qd[i] = p7[i];
-        } else {
-            double qv[7];
-            se3_plus(p7, dcs + 6 * fidx, qv);
-#pragma unroll
-            for (int i = 0; i < 7; ++i) qd[i] = qv[i];
-        }
-    }
-    if (lane == 0) k5_result(st, 1, d2, gd);
-    STAMP(5);
-}
+#include "ba_k5_x2.hpp"  // K5 on the VALU, two rows per lane (11..20 free keyframes)
 
 // ---------------------------------------------------------------------------------------
 // K6: one wave per landmark group: back-substitution dp = V^-1 (-g_p - W^T dc), the trial
@@ -3264,21 +2334,12 @@ __global__ __launch_bounds__(64 * kX2Waves) void ba_camera_solve_x2(Geometry G, 
 //      (slot_linearize<COST_ONLY>), no Jacobian blocks and no records.  Should the decision
 //      accept the trial and the solve go on, the host runs this iteration's full K6 again before
 //      the next chunk (enqueue_chunk): same inputs, same trial, plus the records.
-#ifndef RSVIO_EXPORT_FENCE  // build-time A/B: 1 = a full system-scope release fence at the end of
-#define RSVIO_EXPORT_FENCE 0  // every exporting wave (an L2 write-back per wave)
-#endif
 // The end of a wave that wrote into the export buffer: its stores have been acknowledged.  The
 // buffer is fine-grained (uncached) host memory, so an acknowledged store has left the L2 -- and
 // K7's slot stamps, system-scope releases by blocks on every XCD, each write its L2 back first.
-// (A full release fence here made every wave write the L2 back while the others still store
-// their trial points: K6 7.5 us instead of 5.4.)
-__device__ __forceinline__ void export_done() {
-#if RSVIO_EXPORT_FENCE
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-#else
-    __builtin_amdgcn_s_waitcnt(kWaitStores);
-#endif
-}
+// (A full system-scope release fence here made every wave write the L2 back while the others
+// still store their trial points: K6 7.5 us instead of 5.4, profiles/r07_last_k6_kstats.txt.)
+__device__ __forceinline__ void export_done() { __builtin_amdgcn_s_waitcnt(kWaitStores); }
 template <bool FUSED, bool LAST = false>
 __device__ void k6_body(const Geometry& G, const Prob& Pr, const Work& Wk, int w, int lane, double (*sh)[64],
                         double (*shp)[64], double (*shs)[64], const P2P* PP = nullptr,
@@ -3807,10 +2868,7 @@ __global__ __launch_bounds__(64) void ba_reduce_trial(Geometry G, Prob Pr, Work 
 // the chunk's last K6 has exported that very buffer of this solve (k6_body's LAST form; its tag
 // in tick[2], tick[3]): a solve that ends without applying its last candidate, the usual end.
 constexpr int kK7Threads = 256;
-#ifndef RSVIO_K7_BLOCKS  // build-time A/B: 48 blocks measured no faster and less stable
-#define RSVIO_K7_BLOCKS 16  // (profiles/r03w_k7_blocks_ab.txt)
-#endif
-constexpr int kK7Blocks = RSVIO_K7_BLOCKS;
+constexpr int kK7Blocks = 16;  // 48 blocks measured no faster and less stable (profiles/r03w_k7_blocks_ab.txt)
 __device__ __forceinline__ void lm_decide_body(const Geometry& G, const Prob& Pr, const Work& Wk, int pre_reduced,
                                                const LmArgs& la, LmState* host, unsigned long long* htick,
                                                double* hout, const P2P* PP = nullptr,
@@ -5035,46 +4093,36 @@ struct BundleAdjuster {
     void launch_camera_solve(const Prob& pr, const Work& wk, int combine) {
         if (combine && wide_combine()) combine = 0;
         const dim3 g(1), b(kK5Threads);
-        if (k5_variant == 2 && G.n_free <= 10) {
-            switch (G.n_free) {
-#define RSVIO_CAMM(NF) \
-    case NF: hipLaunchKernelGGL(ba_camera_solve_mfma<NF>, g, b, 0, stream, G, pr, wk, combine); break;
-                RSVIO_CAMM(1) RSVIO_CAMM(2) RSVIO_CAMM(3) RSVIO_CAMM(4) RSVIO_CAMM(5)
-                RSVIO_CAMM(6) RSVIO_CAMM(7) RSVIO_CAMM(8) RSVIO_CAMM(9) RSVIO_CAMM(10)
-#undef RSVIO_CAMM
-                default: break;
-            }
+        if (k5_variant == 2 && G.n_free <= 10) {  // (no free keyframe: nothing to launch)
+            dispatch_panel_nf(G.n_free, [&](auto nf) {
+                constexpr int NF = decltype(nf)::value;
+                hipLaunchKernelGGL(ba_camera_solve_mfma<NF>, g, b, 0, stream, G, pr, wk, combine);
+            });
             RSVIO_HIP(hipGetLastError());
             return;
         }
-        switch (G.n_free <= 10 ? G.n_free : 0) {
-#define RSVIO_CAM(NF) \
-    case NF: hipLaunchKernelGGL(ba_camera_solve<NF>, g, b, 0, stream, G, pr, wk, combine, k5_variant); break;
-            RSVIO_CAM(1) RSVIO_CAM(2) RSVIO_CAM(3) RSVIO_CAM(4) RSVIO_CAM(5)
-            RSVIO_CAM(6) RSVIO_CAM(7) RSVIO_CAM(8) RSVIO_CAM(9) RSVIO_CAM(10)
-#undef RSVIO_CAM
-            default: {
-                if (k5_variant == 2) {  // the 6x6-block solver with MFMA updates (the default)
-                    const dim3 b3(64 * kBkWaves);
-                    // sharded: the all-reduced system couples the keyframes of every rank's
-                    // landmarks, G.env only this rank's (it still bounds this rank's chunks) --
-                    // the factorisation takes the dense envelope.  Decided here, at the launch, so
-                    // that the order of attach and set_problem cannot matter.
-                    Geometry Gk = G;
-                    if (sharded()) rsvio_env::dense_envelope(G.n_free, Gk.env);
-                    switch (bk_template_nf(G.n_free)) {
-                        case 13: hipLaunchKernelGGL(ba_camera_solve_blk<13>, g, b3, 0, stream, Gk, pr, wk, combine); break;
-                        case 16: hipLaunchKernelGGL(ba_camera_solve_blk<16>, g, b3, 0, stream, Gk, pr, wk, combine); break;
-                        default: hipLaunchKernelGGL(ba_camera_solve_blk<20>, g, b3, 0, stream, Gk, pr, wk, combine); break;
-                    }
-                    break;
-                }
-                const dim3 b2(64 * kX2Waves);
-                if (G.n_free <= 13) hipLaunchKernelGGL(ba_camera_solve_x2<13>, g, b2, 0, stream, G, pr, wk, combine);
-                else if (G.n_free <= 16) hipLaunchKernelGGL(ba_camera_solve_x2<16>, g, b2, 0, stream, G, pr, wk, combine);
-                else hipLaunchKernelGGL(ba_camera_solve_x2<20>, g, b2, 0, stream, G, pr, wk, combine);
-                break;
-            }
+        const bool valu = dispatch_panel_nf(G.n_free, [&](auto nf) {
+            constexpr int NF = decltype(nf)::value;
+            hipLaunchKernelGGL(ba_camera_solve<NF>, g, b, 0, stream, G, pr, wk, combine, k5_variant);
+        });
+        if (!valu && k5_variant == 2) {  // the 6x6-block solver with MFMA updates (the default)
+            const dim3 b3(64 * kBkWaves);
+            // sharded: the all-reduced system couples the keyframes of every rank's landmarks, G.env
+            // only this rank's (it still bounds this rank's chunks) -- the factorisation takes the
+            // dense envelope.  Decided here, at the launch, so that the order of attach and
+            // set_problem cannot matter.
+            Geometry Gk = G;
+            if (sharded()) rsvio_env::dense_envelope(G.n_free, Gk.env);
+            dispatch_block_nf(bk_template_nf(G.n_free), [&](auto nf) {
+                constexpr int NF = decltype(nf)::value;
+                hipLaunchKernelGGL(ba_camera_solve_blk<NF>, g, b3, 0, stream, Gk, pr, wk, combine);
+            });
+        } else if (!valu) {
+            const dim3 b2(64 * kX2Waves);
+            dispatch_block_nf(bk_template_nf(G.n_free), [&](auto nf) {
+                constexpr int NF = decltype(nf)::value;
+                hipLaunchKernelGGL(ba_camera_solve_x2<NF>, g, b2, 0, stream, G, pr, wk, combine);
+            });
         }
         RSVIO_HIP(hipGetLastError());
     }
@@ -5100,21 +4148,16 @@ struct BundleAdjuster {
                 hipLaunchKernelGGL(ba_schur_chunks, dim3(G.n_chunk), dim3(kSchurThreads), 0, stream, G, pr, wk,
                                    lm_args(cfg), 1);
             RSVIO_HIP(hipGetLastError());
-            switch (G.n_free) {
-#define RSVIO_CAMP(NF) \
-    case NF:                                                                                                            \
-        if (p2p.ll)                                                                                                     \
-            hipLaunchKernelGGL((ba_camera_solve_mfma_p2p<NF, true>), dim3(1), dim3(kK5Threads), 0, stream, G, pr, wk,  \
-                               p2p, d_xgen.p, d_p2p_err.p);                                                            \
-        else                                                                                                            \
-            hipLaunchKernelGGL((ba_camera_solve_mfma_p2p<NF, false>), dim3(1), dim3(kK5Threads), 0, stream, G, pr, wk, \
-                               p2p, d_xgen.p, d_p2p_err.p);                                                            \
-        break;
-                RSVIO_CAMP(1) RSVIO_CAMP(2) RSVIO_CAMP(3) RSVIO_CAMP(4) RSVIO_CAMP(5)
-                RSVIO_CAMP(6) RSVIO_CAMP(7) RSVIO_CAMP(8) RSVIO_CAMP(9) RSVIO_CAMP(10)
-#undef RSVIO_CAMP
-                default: throw std::logic_error("p2p_fold: more than 10 free keyframes");
-            }
+            const bool k5 = dispatch_panel_nf(G.n_free, [&](auto nf) {
+                constexpr int NF = decltype(nf)::value;
+                if (p2p.ll)
+                    hipLaunchKernelGGL((ba_camera_solve_mfma_p2p<NF, true>), dim3(1), dim3(kK5Threads), 0, stream, G,
+                                       pr, wk, p2p, d_xgen.p, d_p2p_err.p);
+                else
+                    hipLaunchKernelGGL((ba_camera_solve_mfma_p2p<NF, false>), dim3(1), dim3(kK5Threads), 0, stream, G,
+                                       pr, wk, p2p, d_xgen.p, d_p2p_err.p);
+            });
+            if (!k5) throw std::logic_error("p2p_fold: more than 10 free keyframes");
             RSVIO_HIP(hipGetLastError());
         } else {
             enqueue_linear_system(it, lm_args(cfg), false);
@@ -5179,14 +4222,11 @@ struct BundleAdjuster {
         const int wi = it & 1;  // work(it) depends on the parity of it only
         hipLaunchKernelGGL(bab_schur_chunks, dim3(G.n_chunk, 1), dim3(kSchurThreads), 0, stream, dptr(), wi, lm_args(cfg));
         RSVIO_HIP(hipGetLastError());
-        switch (G.n_free) {
-#define RSVIO_CAMD(NF) \
-    case NF: hipLaunchKernelGGL(bab_camera_solve<NF>, dim3(1), dim3(kK5Threads), 0, stream, dptr(), wi); break;
-            RSVIO_CAMD(1) RSVIO_CAMD(2) RSVIO_CAMD(3) RSVIO_CAMD(4) RSVIO_CAMD(5)
-            RSVIO_CAMD(6) RSVIO_CAMD(7) RSVIO_CAMD(8) RSVIO_CAMD(9) RSVIO_CAMD(10)
-#undef RSVIO_CAMD
-            default: throw std::logic_error("descriptor mode: more than 10 free keyframes");
-        }
+        const bool k5 = dispatch_panel_nf(G.n_free, [&](auto nf) {
+            constexpr int NF = decltype(nf)::value;
+            hipLaunchKernelGGL(bab_camera_solve<NF>, dim3(1), dim3(kK5Threads), 0, stream, dptr(), wi);
+        });
+        if (!k5) throw std::logic_error("descriptor mode: more than 10 free keyframes");
         RSVIO_HIP(hipGetLastError());
         if (last && lean_last())
             hipLaunchKernelGGL(bab_backsub_trial_export, dim3(wcap, 1), dim3(64), 0, stream, dptr(), wi, h_out.p);
@@ -5759,15 +4799,14 @@ struct BundleAdjuster {
                            LmArgs{1, 0.0, 0.0}, 0);
         {
             const dim3 g(1), b(kK5Threads), b3(64 * kBkWaves);
-            switch (G.n_free <= 10 ? G.n_free : bk_template_nf(G.n_free)) {
-#define RSVIO_COVC(NF) \
-    case NF: hipLaunchKernelGGL(ba_camera_covariance<NF>, g, NF <= 10 ? b : b3, 0, stream, Gc, pr, wk, O); break;
-                RSVIO_COVC(1) RSVIO_COVC(2) RSVIO_COVC(3) RSVIO_COVC(4) RSVIO_COVC(5)
-                RSVIO_COVC(6) RSVIO_COVC(7) RSVIO_COVC(8) RSVIO_COVC(9) RSVIO_COVC(10)
-                RSVIO_COVC(13) RSVIO_COVC(16) RSVIO_COVC(20)
-#undef RSVIO_COVC
-                default: break;
-            }
+            auto launch = [&](auto nf) {
+                constexpr int NF = decltype(nf)::value;
+                hipLaunchKernelGGL(ba_camera_covariance<NF>, g, NF <= 10 ? b : b3, 0, stream, Gc, pr, wk, O);
+            };
+            if (G.n_free <= 10)
+                dispatch_panel_nf(G.n_free, launch);
+            else
+                dispatch_block_nf(bk_template_nf(G.n_free), launch);
         }
         hipLaunchKernelGGL(ba_landmark_covariance, dim3(std::max(G.n_wave + (n_lm + 63) / 64, 1)), dim3(64), 0, stream,
                            Gc, pr, wk, reinterpret_cast<const unsigned long long*>(d_arena.p + lay.mask), d_sel, O);
@@ -5909,17 +4948,14 @@ struct BundleBatch {
 
     void launch_k5(int nf, int wi) {
         const int B = (int)win.size();
-        switch (nf) {
-#define RSVIO_BAB(NF) \
-    case NF: hipLaunchKernelGGL(bab_camera_solve<NF>, dim3(B), dim3(kK5Threads), 0, stream, d_desc.p, wi); break;
-            RSVIO_BAB(1) RSVIO_BAB(2) RSVIO_BAB(3) RSVIO_BAB(4) RSVIO_BAB(5)
-            RSVIO_BAB(6) RSVIO_BAB(7) RSVIO_BAB(8) RSVIO_BAB(9) RSVIO_BAB(10)
-#undef RSVIO_BAB
-            case 13: hipLaunchKernelGGL(bab_camera_solve_blk<13>, dim3(B), dim3(64 * kBkWaves), 0, stream, d_desc.p, wi); break;
-            case 16: hipLaunchKernelGGL(bab_camera_solve_blk<16>, dim3(B), dim3(64 * kBkWaves), 0, stream, d_desc.p, wi); break;
-            case 20: hipLaunchKernelGGL(bab_camera_solve_blk<20>, dim3(B), dim3(64 * kBkWaves), 0, stream, d_desc.p, wi); break;
-            default: throw std::logic_error("batched mode: no camera-solve template for this window size");
-        }
+        const bool k5 = dispatch_panel_nf(nf, [&](auto c) {
+            constexpr int NF = decltype(c)::value;
+            hipLaunchKernelGGL(bab_camera_solve<NF>, dim3(B), dim3(kK5Threads), 0, stream, d_desc.p, wi);
+        }) || dispatch_block_nf(nf, [&](auto c) {
+            constexpr int NF = decltype(c)::value;
+            hipLaunchKernelGGL(bab_camera_solve_blk<NF>, dim3(B), dim3(64 * kBkWaves), 0, stream, d_desc.p, wi);
+        });
+        if (!k5) throw std::logic_error("batched mode: no camera-solve template for this window size");
         RSVIO_HIP(hipGetLastError());
     }
 
