@@ -684,6 +684,70 @@ int rsvio_pnp_batch_track_motion_robust(rsvio_pnp_batch* b, const rsvio_motion_f
                                         rsvio_robust_motion_result* results, double* device_ms);
 void rsvio_pnp_batch_destroy(rsvio_pnp_batch* b);
 
+/* Motion covariance: the 6x6 covariance of a frame's pose from the PnP Hessian (no reference
+ * counterpart; the per-frame companion of rsvio_ba_covariance).  One single-workgroup launch per
+ * frame, one pass over the features: no LM runs, no existing call changes.
+ *   Pose.  x is T_B_W = inverse(T_W_B) of the T_W_B the caller passes (a rigid inverse in f64 on
+ * the host) -- the pose the caller was given back, not the LM's internal 7-vector.  It need not be
+ * a minimum of the cost.
+ *   Factors.  A feature of the left list, then of the right list, in list order, is a factor iff
+ * its id has a map point (rsvio_track_motion's lookup) and its mask byte is 1, or no mask was given
+ * for that list.  A mask byte of 1 on a feature without a map point is ignored: the masks are
+ * exactly what rsvio_track_motion_robust writes (1 = inlier).
+ *   H = sum_factors w J^T J with no damping: J is the PnP factor's 2x6 [dt | dw], w the Huber IRLS
+ * weight at huber_delta, in the tangent the LM's (+) uses (T_B_W <- T_B_W Exp([dt; dw])) -- the
+ * convention of rsvio_ba_covariance's pose blocks, so a frame's covariance and a keyframe's are
+ * comparable.
+ *   cov36 = H^-1, 6x6 row-major, symmetric bit for bit, per unit measurement variance in
+ * normalised-image-coordinate^2: the caller multiplies by its sigma^2.  Because
+ * T_W_B' = Exp(-d) T_W_B, it is also the covariance of T_W_B under a LEFT (world-side) perturbation.
+ * info->status:
+ *   RSVIO_MCOV_OK        cov36 is H^-1
+ *   RSVIO_MCOV_TOO_FEW   fewer than 3 factors (six rows for six unknowns); also no factor at all,
+ *                        an empty map or a handle without a map
+ *   RSVIO_MCOV_SINGULAR  an LDL^T pivot of H is not positive and finite (the solver's and the BA
+ *                        covariance's rule), e.g. a non-finite T_W_B or a point on a camera's z = 0
+ * On a status other than OK the 36 outputs are NaN; the function still returns RSVIO_OK.  A
+ * geometry degenerate only up to rounding may report OK with a huge covariance or SINGULAR.
+ * info: n_observations the factors used, n_downweighted those with w < 1, cost = sum rho / 2 over
+ * the factors (rsvio_motion_result.final_cost's definition), min_pivot the smallest pivot (the
+ * first one that failed on SINGULAR, 0 when nothing was factorised), kernel_ms as in
+ * rsvio_motion_result.  Every sum runs in a fixed order: two calls give the same bits, and slot i
+ * of the batched call gives the single call's on handle i.
+ *   The calls run on the handle's active stream (the batch call on the batch's: one upload, one
+ * launch, one host wait) and neither read nor change the map or anything a tracking call left.
+ * Everything is checked before anything is launched or written: a NULL required pointer, or
+ * huber_delta <= 0 or NaN, is RSVIO_ERR_INVALID_ARG; n_l + n_r > 4096 is RSVIO_ERR_CAPACITY (the
+ * batch names the slot in rsvio_last_error). */
+enum { RSVIO_MCOV_OK = 1, RSVIO_MCOV_TOO_FEW = -1, RSVIO_MCOV_SINGULAR = -2 };
+typedef struct {
+    int32_t status;           /* RSVIO_MCOV_* */
+    int32_t n_observations;   /* factors used */
+    int32_t n_downweighted;   /* ... with a Huber weight below 1 */
+    int32_t reserved;
+    double cost;              /* sum rho / 2 over the factors */
+    double min_pivot;         /* smallest LDL^T pivot; 0 if not factorised */
+    double kernel_ms;         /* device wall clock, as rsvio_motion_result.kernel_ms */
+} rsvio_motion_cov_info;      /* 40 bytes */
+int rsvio_motion_covariance(rsvio_pnp* p, const uint64_t* ids_l, const float* uv_l, size_t n_l,
+                            const uint64_t* ids_r, const float* uv_r, size_t n_r,
+                            const uint8_t* mask_l, const uint8_t* mask_r,  /* n_l, n_r bytes, or NULL: every joined feature */
+                            const double* T_W_B, const double* T_C_B2, double huber_delta,
+                            double* cov36, rsvio_motion_cov_info* info);
+/* Same for the tracker's last collected frame, read in place on the device (as
+ * rsvio_track_motion_tracker, with its preconditions); mask_l / mask_r are host arrays indexed
+ * like the collected feature lists. */
+int rsvio_motion_covariance_tracker(rsvio_pnp* p, rsvio_tracker* t, const uint8_t* mask_l, const uint8_t* mask_r,
+                                    const double* T_W_B, const double* T_C_B2, double huber_delta,
+                                    double* cov36, rsvio_motion_cov_info* info);
+/* Batched: the frame table of rsvio_pnp_batch_track_motion*, one launch on a grid of n.  Read per
+ * slot: the lists (on_device 0 or 1, id_stride), T_C_B2, and mask_l / mask_r as INPUTS when
+ * non-NULL (host arrays: the ones the robust batch call filled); cfg, samples, hyp_count and
+ * T_W_B_last_kf are ignored.  T_W_B holds slot i's pose at 16 i, cov its covariance at 36 i. */
+int rsvio_pnp_batch_covariance(rsvio_pnp_batch* b, const rsvio_motion_frame* frames, const double* T_W_B /* n x 16 */,
+                               double huber_delta, double* cov /* n x 36 */, rsvio_motion_cov_info* info /* n */,
+                               double* device_ms /* may be NULL */);
+
 /* Batched tracker (the serving mode's first leg): n StereoPatchTracker handles and ONE stereo frame
  * per handle tracked by one call -- one upload (the staged host images and the descriptor tables),
  * three launches whatever n is (pyramids + FAST-9 of all 2n images; one LK launch of up to 3n

@@ -663,6 +663,7 @@ __global__ __launch_bounds__(kPnpThreads) void pnp_track_motion_batch_kernel(con
 }
 
 #include "pnp_robust.hpp"
+#include "pnp_covariance.hpp"
 
 }  // namespace
 
@@ -694,6 +695,17 @@ struct Pnp {
     HostBuf<int> hrint;                  // samples (staging), hyp_count (read back)
     HostBuf<uint8_t> hrmask;
     hipEvent_t rev[2] = {nullptr, nullptr};
+    // the covariance call's (pnp_covariance.hpp), allocated by its first call
+    HostBuf<CovOut> hcov;
+    DevBuf<uint8_t> cmask;               // [mask_l | mask_r]
+    HostBuf<uint8_t> hcmask;
+
+    void init_cov() {
+        if (hcov.p) return;
+        cmask.alloc(kPnpMaxFeatures);
+        hcmask.alloc(kPnpMaxFeatures);
+        hcov.alloc(1);
+    }
 
     void init_robust() {
         if (rev[1]) return;
@@ -914,6 +926,55 @@ int run_pnp_robust(Pnp& p, PnpArgs A, hipStream_t stream, const rsvio_ransac_cfg
     return RSVIO_OK;
 }
 
+// ---- motion covariance (pnp_covariance.hpp) ----
+
+// The arguments of one covariance launch on handle p at T_W_B, lists not yet set: the map, and
+// T_C_W = T_C_B inverse(T_W_B) per camera.  Touches nothing a tracking call reads (make_args
+// caches the last keyframe's quaternion; this does not go through it).
+CovArgs cov_args(const Pnp& p, const double* T_W_B, const double* TCB2, double huber_delta) {
+    CovArgs A{};
+    A.P.table = p.table.p;
+    A.P.bucket_mask = p.bucket_mask;
+    A.P.max_probe = p.max_probe;
+    A.P.has_top = p.has_top;
+    for (int k = 0; k < 3; ++k) A.P.top_pw[k] = p.top_pw[k];
+    A.P.n_map = p.n_map;
+    A.P.wclk_khz = p.wclk_khz;
+    A.huber_delta = huber_delta;
+    double TBW[16];
+    rigid_inverse(T_W_B, TBW);
+    for (int c = 0; c < 2; ++c) {
+        const double* T = TCB2 + 16 * c;
+        for (int i = 0; i < 3; ++i) {
+            for (int j = 0; j < 3; ++j)
+                A.TCW[c][3 * i + j] = (T[4 * i] * TBW[j] + T[4 * i + 1] * TBW[4 + j]) + T[4 * i + 2] * TBW[8 + j];
+            A.TCW[c][9 + i] = ((T[4 * i] * TBW[3] + T[4 * i + 1] * TBW[7]) + T[4 * i + 2] * TBW[11]) + T[4 * i + 3];
+        }
+    }
+    return A;
+}
+
+// One launch on `stream`, then the host wait; A.P holds the lists (device pointers and counts,
+// n_l + n_r <= kPnpMaxFeatures), the masks are host arrays or null
+int run_pnp_cov(Pnp& p, CovArgs A, hipStream_t stream, const uint8_t* mask_l, const uint8_t* mask_r, double* cov36,
+                rsvio_motion_cov_info* info) {
+    p.init_cov();
+    const size_t n_l = (size_t)A.P.n[0], n_r = (size_t)A.P.n[1];
+    if (mask_l && n_l) std::memcpy(p.hcmask.p, mask_l, n_l);
+    if (mask_r && n_r) std::memcpy(p.hcmask.p + n_l, mask_r, n_r);
+    if ((mask_l && n_l) || (mask_r && n_r))
+        RSVIO_HIP(hipMemcpyAsync(p.cmask.p, p.hcmask.p, n_l + n_r, hipMemcpyHostToDevice, stream));
+    A.mask[0] = mask_l ? p.cmask.p : nullptr;
+    A.mask[1] = mask_r ? p.cmask.p + n_l : nullptr;
+    A.out = p.hcov.p;
+    hipLaunchKernelGGL(pnp_covariance_kernel, dim3(1), dim3(kPnpThreads), 0, stream, A);
+    RSVIO_HIP(hipGetLastError());
+    RSVIO_HIP(hipStreamSynchronize(stream));
+    std::memcpy(cov36, p.hcov.p->cov, sizeof p.hcov.p->cov);
+    *info = p.hcov.p->info;
+    return RSVIO_OK;
+}
+
 // ---- batched motion tracking: one frame per handle, all in one launch chain ----
 
 constexpr int kPnpBatchMax = 4096;       // handles per batch
@@ -940,6 +1001,7 @@ struct PnpBatch {
     DevBuf<uint8_t> rmask;             // mask: stream i at i * (the call's mask stride)
     HostBuf<int> hcount;
     HostBuf<uint8_t> hmask;
+    HostBuf<CovOut> hcov;              // the covariance kernel's result table
     double device_ms = 0.0;
 
     static constexpr size_t kDblPerStream = 11 * (size_t)kPnpMaxFeatures + 12 * (size_t)kRansacMaxHyp;
@@ -1012,8 +1074,9 @@ int batch_cap(const PnpBatch& b, const rsvio_motion_frame* frames) {
 }
 
 // Lay the call's image out (table of n entries of `entry` bytes, host frames, samples of
-// `samp_bytes` each where given) and stage the host frames and samples; returns its size
-size_t batch_stage(PnpBatch& b, const rsvio_motion_frame* frames, size_t entry, size_t samp_bytes) {
+// `samp_bytes` each where given, then `extra` bytes the caller fills) and stage the host frames and
+// samples; returns the size without the extra bytes, i.e. their offset
+size_t batch_stage(PnpBatch& b, const rsvio_motion_frame* frames, size_t entry, size_t samp_bytes, size_t extra = 0) {
     size_t off = align16(entry * (size_t)b.n);
     for (int i = 0; i < b.n; ++i) {
         const rsvio_motion_frame& f = frames[i];
@@ -1022,7 +1085,7 @@ size_t batch_stage(PnpBatch& b, const rsvio_motion_frame* frames, size_t entry, 
         b.samp_off[i] = off;
         if (samp_bytes && f.samples) off += align16(samp_bytes);
     }
-    b.reserve_image(off);
+    b.reserve_image(off + extra);
     for (int i = 0; i < b.n; ++i) {
         const rsvio_motion_frame& f = frames[i];
         if (!f.on_device) {
@@ -1038,10 +1101,8 @@ size_t batch_stage(PnpBatch& b, const rsvio_motion_frame* frames, size_t entry, 
     return off;
 }
 
-// Slot i's PnpArgs: handle i's current map, frame i's poses, cfg and lists
-PnpArgs batch_args(PnpBatch& b, int i, const rsvio_motion_frame& f, const rsvio_lm_cfg* cfg,
-                   const rsvio_keyframe_rule* rule) {
-    PnpArgs A = make_args(*b.h[i], f.T_W_B_last_kf, f.T_C_B2, f.cfg ? f.cfg : cfg, rule);
+// Slot i's lists in A: device pointers read in place, or the frame staged in the call's image
+void batch_lists(const PnpBatch& b, int i, const rsvio_motion_frame& f, PnpArgs& A) {
     if (f.on_device) {  // device pointers, read in place
         A.ids[0] = reinterpret_cast<const uint8_t*>(f.ids_l);
         A.ids[1] = reinterpret_cast<const uint8_t*>(f.ids_r);
@@ -1060,6 +1121,13 @@ PnpArgs batch_args(PnpBatch& b, int i, const rsvio_motion_frame& f, const rsvio_
     A.dcount = nullptr;
     A.n[0] = (int)f.n_l;
     A.n[1] = (int)f.n_r;
+}
+
+// Slot i's PnpArgs: handle i's current map, frame i's poses, cfg and lists
+PnpArgs batch_args(PnpBatch& b, int i, const rsvio_motion_frame& f, const rsvio_lm_cfg* cfg,
+                   const rsvio_keyframe_rule* rule) {
+    PnpArgs A = make_args(*b.h[i], f.T_W_B_last_kf, f.T_C_B2, f.cfg ? f.cfg : cfg, rule);
+    batch_lists(b, i, f, A);
     return A;
 }
 
@@ -1179,6 +1247,73 @@ int run_pnp_batch_robust(PnpBatch& b, const rsvio_motion_frame* frames, const rs
         if (f.mask_l && f.n_l) std::memcpy(f.mask_l, m, f.n_l);
         if (f.mask_r && f.n_r) std::memcpy(f.mask_r, m + f.n_l, f.n_r);
         if (f.hyp_count) std::memcpy(f.hyp_count, b.hcount.p + n_hyp * i, sizeof(int32_t) * n_hyp);
+    }
+    return RSVIO_OK;
+}
+
+// The host-side checks of the batched covariance call (it reads no cfg and no T_W_B_last_kf)
+int batch_cov_check(const PnpBatch& b, const rsvio_motion_frame* frames) {
+    for (int i = 0; i < b.n; ++i) {
+        const rsvio_motion_frame& f = frames[i];
+        if (!f.T_C_B2 || (f.n_l && (!f.ids_l || !f.uv_l)) || (f.n_r && (!f.ids_r || !f.uv_r)) || f.id_stride < 0 ||
+            (f.id_stride && f.id_stride < 8)) {
+            char msg[96];
+            std::snprintf(msg, sizeof msg, "rsvio_pnp_batch_covariance: slot %d: a NULL argument or a bad id_stride", i);
+            set_last_error(msg);
+            return RSVIO_ERR_INVALID_ARG;
+        }
+    }
+    for (int i = 0; i < b.n; ++i)
+        if (frames[i].n_l > (size_t)kPnpMaxFeatures || frames[i].n_r > (size_t)kPnpMaxFeatures ||
+            frames[i].n_l + frames[i].n_r > (size_t)kPnpMaxFeatures) {
+            char msg[96];
+            std::snprintf(msg, sizeof msg, "rsvio_pnp_batch_covariance: slot %d: more than 4096 features in one frame",
+                          i);
+            set_last_error(msg);
+            return RSVIO_ERR_CAPACITY;
+        }
+    return RSVIO_OK;
+}
+
+// One upload (the argument table, the host frames, the masks), one launch on a grid of n, one wait
+int run_pnp_batch_cov(PnpBatch& b, const rsvio_motion_frame* frames, const double* T_W_B, double huber_delta,
+                      double* cov, rsvio_motion_cov_info* info, double* device_ms) {
+    RSVIO_HIP(hipSetDevice(b.device));
+    if (!b.hcov.p) b.hcov.alloc(b.n);
+    size_t mbytes = 0;  // a slot's masks as [mask_l | mask_r], each slot at a 16-byte-aligned offset
+    for (int i = 0; i < b.n; ++i)
+        if (frames[i].mask_l || frames[i].mask_r) mbytes += align16(frames[i].n_l + frames[i].n_r);
+    const size_t moff = batch_stage(b, frames, sizeof(CovArgs), 0, mbytes);
+    CovArgs* tab = reinterpret_cast<CovArgs*>(b.himg.p);
+    size_t off = moff;
+    for (int i = 0; i < b.n; ++i) {
+        const rsvio_motion_frame& f = frames[i];
+        CovArgs A = cov_args(*b.h[i], T_W_B + 16 * i, f.T_C_B2, huber_delta);
+        batch_lists(b, i, f, A.P);
+        if (f.mask_l || f.mask_r) {
+            if (f.mask_l && f.n_l) std::memcpy(b.himg.p + off, f.mask_l, f.n_l);
+            if (f.mask_r && f.n_r) std::memcpy(b.himg.p + off + f.n_l, f.mask_r, f.n_r);
+            A.mask[0] = f.mask_l ? b.dimg.p + off : nullptr;
+            A.mask[1] = f.mask_r ? b.dimg.p + off + f.n_l : nullptr;
+            off += align16(f.n_l + f.n_r);
+        }
+        A.out = b.hcov.p + i;
+        tab[i] = A;
+    }
+    RSVIO_HIP(hipMemcpyAsync(b.dimg.p, b.himg.p, moff + mbytes, hipMemcpyHostToDevice, b.stream));
+    RSVIO_HIP(hipEventRecord(b.ev[0], b.stream));
+    hipLaunchKernelGGL(pnp_covariance_batch_kernel, dim3(b.n), dim3(kPnpThreads), 0, b.stream,
+                       reinterpret_cast<const CovArgs*>(b.dimg.p));
+    RSVIO_HIP(hipGetLastError());
+    RSVIO_HIP(hipEventRecord(b.ev[1], b.stream));
+    RSVIO_HIP(hipStreamSynchronize(b.stream));
+    float ms = 0.f;
+    RSVIO_HIP(hipEventElapsedTime(&ms, b.ev[0], b.ev[1]));
+    b.device_ms = ms;
+    if (device_ms) *device_ms = ms;
+    for (int i = 0; i < b.n; ++i) {
+        std::memcpy(cov + 36 * (size_t)i, b.hcov.p[i].cov, sizeof b.hcov.p[i].cov);
+        info[i] = b.hcov.p[i].info;
     }
     return RSVIO_OK;
 }
@@ -1397,6 +1532,48 @@ int rsvio_pnp_batch_track_motion_robust(rsvio_pnp_batch* b, const rsvio_motion_f
     if (rc != RSVIO_OK) return rc;
     return guarded(
         [&] { return rsvio::run_pnp_batch_robust(b->b, frames, cfg, rule, ransac, results, device_ms); });
+}
+
+int rsvio_motion_covariance(rsvio_pnp* h, const uint64_t* ids_l, const float* uv_l, size_t n_l, const uint64_t* ids_r,
+                            const float* uv_r, size_t n_r, const uint8_t* mask_l, const uint8_t* mask_r,
+                            const double* T_W_B, const double* T_C_B2, double huber_delta, double* cov36,
+                            rsvio_motion_cov_info* info) {
+    if (!h || !T_W_B || !T_C_B2 || !cov36 || !info || (n_l && (!ids_l || !uv_l)) || (n_r && (!ids_r || !uv_r)) ||
+        !(huber_delta > 0.0))  // (NaN fails >)
+        return RSVIO_ERR_INVALID_ARG;
+    if (n_l > (size_t)rsvio::kPnpMaxFeatures || n_r > (size_t)rsvio::kPnpMaxFeatures ||
+        n_l + n_r > (size_t)rsvio::kPnpMaxFeatures) {
+        rsvio::set_last_error("motion_covariance: more than 4096 features in one frame");
+        return RSVIO_ERR_CAPACITY;
+    }
+    return guarded([&] {
+        auto& P = h->p;
+        RSVIO_HIP(hipSetDevice(P.device));
+        rsvio::CovArgs A = rsvio::cov_args(P, T_W_B, T_C_B2, huber_delta);
+        rsvio::host_frame(P, ids_l, uv_l, n_l, ids_r, uv_r, n_r, A.P);
+        return rsvio::run_pnp_cov(P, A, P.active(), mask_l, mask_r, cov36, info);
+    });
+}
+
+int rsvio_motion_covariance_tracker(rsvio_pnp* h, rsvio_tracker* t, const uint8_t* mask_l, const uint8_t* mask_r,
+                                    const double* T_W_B, const double* T_C_B2, double huber_delta, double* cov36,
+                                    rsvio_motion_cov_info* info) {
+    if (!h || !t || !T_W_B || !T_C_B2 || !cov36 || !info || !(huber_delta > 0.0)) return RSVIO_ERR_INVALID_ARG;
+    return guarded([&] {
+        auto& P = h->p;
+        rsvio::CovArgs A = rsvio::cov_args(P, T_W_B, T_C_B2, huber_delta);
+        const int rc = rsvio::tracker_frame(P, t, A.P);
+        if (rc != RSVIO_OK) return rc;
+        return rsvio::run_pnp_cov(P, A, P.active(), mask_l, mask_r, cov36, info);
+    });
+}
+
+int rsvio_pnp_batch_covariance(rsvio_pnp_batch* b, const rsvio_motion_frame* frames, const double* T_W_B,
+                               double huber_delta, double* cov, rsvio_motion_cov_info* info, double* device_ms) {
+    if (!b || !frames || !T_W_B || !cov || !info || !(huber_delta > 0.0)) return RSVIO_ERR_INVALID_ARG;
+    const int rc = rsvio::batch_cov_check(b->b, frames);
+    if (rc != RSVIO_OK) return rc;
+    return guarded([&] { return rsvio::run_pnp_batch_cov(b->b, frames, T_W_B, huber_delta, cov, info, device_ms); });
 }
 
 }  // extern "C"

@@ -97,6 +97,15 @@ class MotionFrame(C.Structure):
                 ("on_device", C.c_int32), ("id_stride", C.c_int32)]
 
 
+class MotionCovInfo(C.Structure):
+    """rsvio_motion_cov_info (40 B): the outcome of rsvio_motion_covariance*."""
+    _fields_ = [("status", C.c_int32), ("n_observations", C.c_int32), ("n_downweighted", C.c_int32),
+                ("reserved", C.c_int32), ("cost", C.c_double), ("min_pivot", C.c_double), ("kernel_ms", C.c_double)]
+
+
+MCOV_STATUS = {1: "Ok", -1: "TooFew", -2: "Singular"}
+
+
 class StereoFrame(C.Structure):
     """rsvio_stereo_frame (80 B): one slot's frame of rsvio_tracker_batch_process_frames."""
     _fields_ = [("left", C.c_void_p), ("right", C.c_void_p), ("stride", C.c_size_t),
@@ -192,6 +201,10 @@ SIG = {
     "rsvio_pnp_batch_track_motion_robust": (C.c_int, [P, P, C.POINTER(LmCfg), C.POINTER(KeyframeRule),
                                                       C.POINTER(RansacCfg), P, C.POINTER(C.c_double)]),
     "rsvio_pnp_batch_destroy": (None, [P]),
+    "rsvio_motion_covariance": (C.c_int, [P, P, P, C.c_size_t, P, P, C.c_size_t, P, P, P, P, C.c_double, P,
+                                          C.POINTER(MotionCovInfo)]),
+    "rsvio_motion_covariance_tracker": (C.c_int, [P, P, P, P, P, P, C.c_double, P, C.POINTER(MotionCovInfo)]),
+    "rsvio_pnp_batch_covariance": (C.c_int, [P, P, P, C.c_double, P, P, C.POINTER(C.c_double)]),
     "rsvio_tracker_batch_create": (C.c_int, [P, C.c_int32, C.POINTER(P)]),
     "rsvio_tracker_batch_process_frames": (C.c_int, [P, P, C.POINTER(C.c_double)]),
     "rsvio_tracker_batch_destroy": (None, [P]),

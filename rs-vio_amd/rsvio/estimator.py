@@ -41,6 +41,7 @@ class FrameResult:
     pnp_iterations: int | None = None   # LM iterations of the motion tracking
     pnp_cost: float | None = None       # its final cost
     ba_iterations: int | None = None    # LM iterations of the window's solve (the retry's, after a fallback)
+    pose_covariance: np.ndarray | None = None   # Estimator(pose_covariance=True): 6x6 of T_W_B when pnp_status > 0
 
 
 class DeviceBackend:
@@ -109,6 +110,11 @@ class DeviceBackend:
         m = r.motion
         return m.status, m.is_keyframe, m.T_W_B, m.iterations, m.final_cost, r
 
+    def pose_covariance(self, T_W_B, T_C_B2, huber_delta, mask_l=None, mask_r=None):
+        """The PoseCovariance of T_W_B on the collected frame's device lists (masks: the robust
+        call's, indexed like the collected lists)."""
+        return self.motion.covariance_tracker(self.tracker, T_W_B, T_C_B2, huber_delta, mask_l, mask_r)
+
     def remove_ids(self, ids):
         """StereoPatchTracker::remove_id: the ids leave the tracker before its next frame."""
         self.tracker.remove_id(np.asarray(ids, np.uint64))
@@ -127,7 +133,7 @@ class Estimator:
                  max_iterations: int = 20, thresh: float = 0.01, window: int = 10,
                  translation_threshold: float = 0.05, rotation_threshold: float = 0.05, device: int = 0,
                  backend=None, pipelined: bool = False, landmark_init: str = "ray", gate=None, cull: bool = False,
-                 robust_motion=None, drop_outliers: bool = False):
+                 robust_motion=None, drop_outliers: bool = False, pose_covariance: bool = False):
         # robust_motion: a rsvio.motion.RansacConfig -- the frame's pose and keyframe flag come from
         # MotionTracker.track_motion_tracker_robust (a stereo 3-point RANSAC, the LM on its
         # consensus set) instead of the plain LM over every joined observation; None: the
@@ -138,6 +144,10 @@ class Estimator:
             raise ValueError("drop_outliers needs the tracker idle after motion tracking: not with pipelined=True")
         if drop_outliers and robust_motion is None:
             raise ValueError("drop_outliers needs robust_motion (a RansacConfig)")
+        # pose_covariance: every frame whose motion tracking succeeds also gets the 6x6 covariance of
+        # its T_W_B (MotionTracker.covariance_tracker at the LM cfg's Huber delta, over the robust
+        # call's inliers with robust_motion) in FrameResult.pose_covariance; off: nothing is called
+        self.pose_covariance = pose_covariance
         self.robust_motion = robust_motion
         self.drop_outliers = drop_outliers
         self.last_robust = None       # the last frame's RobustMotionResult
@@ -218,12 +228,13 @@ class Estimator:
         (ids_l, uv_l), (ids_r, uv_r) = feats
         frame = Frame(frame_id=self.frame_id, T_W_B=np.eye(4), T_B_Cl=self.T_B_Cl, T_B_Cr=self.T_B_Cr,
                       is_keyframe=True, left_features=(ids_l, uv_l), right_features=(ids_r, uv_r))
-        pnp_status = pnp_iters = pnp_cost = None
+        pnp_status = pnp_iters = pnp_cost = pose_cov = None
         self.flush()
         if self.window.is_full():
             if self.window.map_version != self._map_key:  # map_points changes only in optimize
                 self.backend.set_map(self.window.map_ids, self.window.map_pw)  # ascending ids, f32
                 self._map_key = self.window.map_version
+            masks = (None, None)
             if self.robust_motion is None:
                 status, is_kf, T_W_B, pnp_iters, pnp_cost = self.backend.track_motion(
                     self.window.keyframes[-1].T_W_B, self._T_C_B2())  # keyframes.back() (sliding_window.rs:506)
@@ -231,6 +242,13 @@ class Estimator:
                 status, is_kf, T_W_B, pnp_iters, pnp_cost, rob = self.backend.track_motion_robust(
                     self.window.keyframes[-1].T_W_B, self._T_C_B2(), self.robust_motion)
                 self.last_robust = rob
+                masks = (rob.mask_l, rob.mask_r)
+            if self.pose_covariance and status > 0:
+                # (before remove_ids: that compacts the device lists the masks are indexed like)
+                from .motion import pnp_cfg
+                c = self.backend.pose_covariance(T_W_B, self._T_C_B2(), pnp_cfg().huber_delta, *masks)
+                pose_cov = c.cov if c.ok else None
+            if self.robust_motion is not None:
                 if self.drop_outliers:
                     out_ids = np.union1d(np.asarray(ids_l)[rob.mask_l == 2], np.asarray(ids_r)[rob.mask_r == 2])
                     self.last_dropped = out_ids.astype(np.uint64)
@@ -254,7 +272,7 @@ class Estimator:
                     ba_iters = None if r is None else int(r.iterations)
         out = FrameResult(self.frame_id, frame.is_keyframe, frame.T_W_B.copy(), len(ids_l), len(ids_r),
                           pnp_status, ba_status, pnp_iterations=pnp_iters, pnp_cost=pnp_cost,
-                          ba_iterations=ba_iters)
+                          ba_iterations=ba_iters, pose_covariance=pose_cov)
         if pending:
             self._pending_frame = (out, frame)
         return out

@@ -97,6 +97,43 @@ def _robust_result(r: _lib.RobustMotionResult, mask_l, mask_r, counts) -> Robust
                               r.best_hyp, r.best_count, r.n_inliers, r.device_ms, mask_l, mask_r, counts)
 
 
+MCOV_OK, MCOV_TOO_FEW, MCOV_SINGULAR = 1, -1, -2
+
+
+@dataclass
+class PoseCovariance:
+    """rsvio_motion_covariance's outcome: cov = H^-1 of the PnP Hessian H = sum w J^T J at
+    T_B_W = inverse(T_W_B), in the LM's tangent (T_B_W <- T_B_W Exp([dt; dw])) -- equally the
+    covariance of T_W_B under the left perturbation Exp(-d) T_W_B -- per unit measurement variance
+    in normalised image units^2.  All NaN unless status is MCOV_OK (MCOV_TOO_FEW: fewer than 3
+    factors; MCOV_SINGULAR: a pivot of H not positive and finite)."""
+    status: int
+    cov: np.ndarray           # 6 x 6, symmetric bit for bit
+    n_observations: int       # factors used
+    n_downweighted: int       # ... with a Huber weight below 1
+    cost: float               # sum rho / 2 over the factors (MotionResult.final_cost's definition)
+    min_pivot: float          # smallest LDL^T pivot (0: not factorised)
+    kernel_ms: float
+
+    @property
+    def ok(self) -> bool:
+        return self.status == MCOV_OK
+
+
+def _pose_cov(cov, i: _lib.MotionCovInfo) -> PoseCovariance:
+    return PoseCovariance(i.status, np.array(cov, np.float64).reshape(6, 6), i.n_observations, i.n_downweighted,
+                          i.cost, i.min_pivot, i.kernel_ms)
+
+
+def _mask(mask, n, what):
+    if mask is None:
+        return None
+    mask = np.ascontiguousarray(mask, np.uint8).reshape(-1)
+    if len(mask) != n:
+        raise ValueError(f"{what} has {len(mask)} bytes for {n} features")
+    return mask
+
+
 class MotionTracker:
     """Device handle for track_motion; holds the map (ids ascending, p_W as f32)."""
 
@@ -209,6 +246,37 @@ class MotionTracker:
                                                             ptr(mask_l), ptr(mask_r), ptr(counts), C.byref(r)))
         return _robust_result(r, mask_l[:n_l].copy(), mask_r[:n_r].copy(), counts)
 
+    def covariance(self, ids_l, uv_l, ids_r, uv_r, T_W_B, T_C_B2, huber_delta: float = 2.0, mask_l=None,
+                   mask_r=None) -> PoseCovariance:
+        """The 6x6 covariance of the pose T_W_B given these features and the handle's map
+        (rsvio_motion_covariance).  mask_l / mask_r: one byte per feature, 1 = use (the masks
+        track_motion_robust returns); None: every feature with a map point."""
+        ids_l = np.ascontiguousarray(ids_l, np.uint64).reshape(-1)
+        ids_r = np.ascontiguousarray(ids_r, np.uint64).reshape(-1)
+        uv_l = np.ascontiguousarray(uv_l, np.float32).reshape(-1, 2)
+        uv_r = np.ascontiguousarray(uv_r, np.float32).reshape(-1, 2)
+        mask_l, mask_r = _mask(mask_l, len(ids_l), "mask_l"), _mask(mask_r, len(ids_r), "mask_r")
+        T = np.ascontiguousarray(T_W_B, np.float64).reshape(16)
+        tcb = np.ascontiguousarray(T_C_B2, np.float64).reshape(32)
+        cov, info = np.empty(36, np.float64), _lib.MotionCovInfo()
+        check(_lib.load().rsvio_motion_covariance(self._h, ptr(ids_l), ptr(uv_l), len(ids_l), ptr(ids_r), ptr(uv_r),
+                                                  len(ids_r), ptr(mask_l), ptr(mask_r), ptr(T), ptr(tcb),
+                                                  float(huber_delta), ptr(cov), C.byref(info)))
+        return _pose_cov(cov, info)
+
+    def covariance_tracker(self, tracker, T_W_B, T_C_B2, huber_delta: float = 2.0, mask_l=None,
+                           mask_r=None) -> PoseCovariance:
+        """covariance() on the tracker's last collected frame, read on the device; the masks are
+        host arrays indexed like the collected feature lists."""
+        n_l, n_r = tracker._n
+        mask_l, mask_r = _mask(mask_l, n_l, "mask_l"), _mask(mask_r, n_r, "mask_r")
+        T = np.ascontiguousarray(T_W_B, np.float64).reshape(16)
+        tcb = np.ascontiguousarray(T_C_B2, np.float64).reshape(32)
+        cov, info = np.empty(36, np.float64), _lib.MotionCovInfo()
+        check(_lib.load().rsvio_motion_covariance_tracker(self._h, tracker._h, ptr(mask_l), ptr(mask_r), ptr(T),
+                                                          ptr(tcb), float(huber_delta), ptr(cov), C.byref(info)))
+        return _pose_cov(cov, info)
+
 
 @dataclass
 class MotionFrame:
@@ -302,7 +370,8 @@ class MotionBatch:
                 c.ids_l, c.uv_l, c.n_l = ptr(ids_l), ptr(uv_l), len(ids_l)
                 c.ids_r, c.uv_r, c.n_r = ptr(ids_r), ptr(uv_r), len(ids_r)
                 keep.append((ids_l, uv_l, ids_r, uv_r))
-            Tl = np.ascontiguousarray(f.T_W_B_last_kf, np.float64).reshape(16)
+            # (None: left NULL -- the covariance call does not read it, the tracking calls refuse)
+            Tl = None if f.T_W_B_last_kf is None else np.ascontiguousarray(f.T_W_B_last_kf, np.float64).reshape(16)
             tcb = np.ascontiguousarray(f.T_C_B2, np.float64).reshape(32)
             c.T_W_B_last_kf, c.T_C_B2 = ptr(Tl), ptr(tcb)
             keep.append((Tl, tcb, f.cfg))
@@ -350,3 +419,29 @@ class MotionBatch:
         del keep
         self.device_ms = ms.value
         return [_robust_result(r, *o) for r, o in zip(res, outs)]
+
+    def covariance(self, frames, T_W_B, huber_delta: float = 2.0, masks=None) -> list[PoseCovariance]:
+        """Slot i's pose covariance at T_W_B[i] (n x 4 x 4) for frames[i] on trackers[i]'s map, all
+        in one launch (rsvio_pnp_batch_covariance); each bit for bit the tracker's own covariance().
+        Of a frame only the lists and T_C_B2 are read.  masks: None, or per slot None or
+        (mask_l, mask_r) -- host arrays, each of which may be None."""
+        tab, keep = self._frames(frames)
+        T = np.ascontiguousarray(T_W_B, np.float64).reshape(self.n, 16)
+        if masks is not None:
+            if len(masks) != self.n:
+                raise ValueError(f"{len(masks)} masks for a batch of {self.n}")
+            for i, m in enumerate(masks):
+                if m is None:
+                    continue
+                ml = _mask(m[0], tab[i].n_l, f"slot {i}: mask_l")
+                mr = _mask(m[1], tab[i].n_r, f"slot {i}: mask_r")
+                tab[i].mask_l, tab[i].mask_r = ptr(ml), ptr(mr)
+                keep.append((ml, mr))
+        cov = np.empty((self.n, 36), np.float64)
+        info = (_lib.MotionCovInfo * self.n)()
+        ms = C.c_double(0.0)
+        check(_lib.load().rsvio_pnp_batch_covariance(self._h, C.addressof(tab), ptr(T), float(huber_delta), ptr(cov),
+                                                     C.addressof(info), C.byref(ms)))
+        del keep
+        self.device_ms = ms.value
+        return [_pose_cov(cov[i], info[i]) for i in range(self.n)]
