@@ -27,12 +27,23 @@
 // cost in a fixed order (DPP reduce-scatter per wave, then the waves in order).  Each pass after
 // the first is at a trial pose: if the step is accepted its H and g are the next system, so an
 // accepted iteration costs one pass.
+//
+// One translation unit: pnp_robust.hpp (the RANSAC in front of this LM) and pnp_covariance.hpp are
+// fragments of it, included inside the file-local namespace after the plain kernel.  What the plain
+// kernel and the robust refit share exists once, here: the LDS of one LM (LmLds<CAP>), the start
+// (prior_pose, ctl_start, ctl_publish), the per-lane T_C_W entry (tcw_entry) and the whole pass loop
+// (lm_passes, the plain kernel's stamps behind a template flag), besides pnp_control and pnp_finish.
+// On the host the entry points share one frame packer and list setter (pack_frame, packed_lists), one
+// timed section (timed_section), and the batched calls one slot check (batch_check) and one launch
+// site per kernel (with_cap picks the LDS capacity).
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
 #include <stdexcept>
+#include <type_traits>
 #include <vector>
 
 #include "common.hpp"
@@ -460,23 +471,151 @@ __device__ __forceinline__ bool map_lookup(const PnpArgs& A, uint64_t id, float 
     return false;
 }
 
+// ---- the LM both bodies run (pnp_track_motion_body here, pnp_robust_refit_body in pnp_robust.hpp) ----
+
+// The LDS of one LM: the factor list (feature j at entry j), the pass sums and the LM state.  Each
+// body declares one __shared__ instance; CAP: the entries for features.  16-byte aligned, and so
+// every array and the state in it (the alignment separate __shared__ variables get: 16-byte LDS
+// accesses); the two ints last, so nothing is padded.
+template <int CAP>
+struct alignas(16) LmLds {
+    float s_mpw[3][CAP];              // the map point per factor
+    float s_uv[2][CAP];               // undistorted coordinates per factor
+    int8_t s_cam[CAP];                // feature -> camera, -1: no factor
+    double s_red[kPnpWaves][kRed];
+    double s_sum[kRed];
+    double s_pose[12];                // R_BW, t_BW of the pass pose (wave 0's)
+    double s_tcb[2][16];
+    double s_tcw[2][12];              // T_C_W = T_C_B T_B_W per camera at the pass pose
+    Ctl s_ctl;                        // the LM state between controls (wave 0's)
+    int s_nobs;                       // the factors
+    int s_run;
+};
+static_assert(offsetof(LmLds<kPnpMaxFeatures>, s_ctl) % 16 == 0, "the LM state in 16-byte LDS accesses");
+
+// Entry e of T_C_W = T_C_B [R | t] as 12 values (R row-major, then t); T: one camera's T_C_B (16),
+// pose: R (9), t (3)
+__device__ __forceinline__ double tcw_entry(const double* T, const double* pose, int e) {
+    if (e < 9) {
+        const int i = e / 3, j = e % 3;
+        return (T[4 * i] * pose[j] + T[4 * i + 1] * pose[3 + j]) + T[4 * i + 2] * pose[6 + j];
+    }
+    const int i = e - 9;
+    return ((T[4 * i] * pose[9] + T[4 * i + 1] * pose[10]) + T[4 * i + 2] * pose[11]) + T[4 * i + 3];
+}
+
+// The pose7 the LM starts from at the last keyframe, T_B_W = inv(T_W_B) with the host's
+// q = UnitQuaternion::from_matrix(R_B_W) (sliding_window.rs:506-517), and its rotation by SE3::from
+// (apex) of that 7-vector
+__device__ __forceinline__ void prior_pose(const PnpArgs& A, double x[7], double R[9]) {
+    double TBW[16];
+    rigid_inverse(A.T_last, TBW);
+    x[0] = TBW[3];
+    x[1] = TBW[7];
+    x[2] = TBW[11];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) x[3 + k] = A.q0[k];
+    const Pose P0 = pose_from7(x);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = P0.R[k / 3][k % 3];
+}
+
+// The LM state before its first pass, all but the pose (x, R)
+__device__ __forceinline__ void ctl_start(const PnpArgs& A, Ctl& C) {
+    C.it = 0;
+    C.status = LM_MAX_ITERS;
+    C.phase = 0;
+    C.lambda = A.lambda0;
+    C.nu = 2.0;
+    C.cost = 0.0;
+    C.initial_cost = 0.0;
+    C.pred = 0.0;
+}
+
+// Lane 0 of wave 0: the start pose as the first pass's, and the state to LDS
+__device__ __forceinline__ void ctl_publish(const Ctl& C, double* s_pose, Ctl& s_ctl) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) s_pose[k] = C.R[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s_pose[9 + k] = C.x[k];
+    s_ctl = C;
+}
+
+// The pass loop: while `run`, one pass at the pose in s_tcw (H, g and the cost over the factors
+// of S, lane t taking entries t, t + 512, ... of the nf features; DPP reduce-scatter per wave, then
+// the waves in order), lane 0's pnp_control, and the next pass's T_C_W by wave 0.  Two workgroup
+// barriers per pass.  STAMPS: the plain kernel's stamp points 3..26 (two per pass, 12 passes).
+template <bool STAMPS, int CAP>
+__device__ __forceinline__ void lm_passes(const PnpArgs& A, LmLds<CAP>& S, int nf, int run) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    int pass = 0;
+    while (run) {
+        if (STAMPS && pass < 12) STAMP(3 + 2 * pass);
+        // one pass at the pose in s_tcw: H, g, cost over this lane's observations (j order)
+        double acc[32];
+#pragma unroll
+        for (int k = 0; k < 32; ++k) acc[k] = 0.0;
+#pragma unroll 1
+        for (int j = tid; j < nf; j += kPnpThreads) {
+            const int cam = S.s_cam[j];
+            if (cam < 0) continue;
+            const double pW[3] = {(double)S.s_mpw[0][j], (double)S.s_mpw[1][j], (double)S.s_mpw[2][j]};
+            const double uv[2] = {(double)S.s_uv[0][j], (double)S.s_uv[1][j]};
+            double r[2], J[2][6];
+            pnp_linearize_cw(pW, uv, S.s_tcw[cam], r, J);
+            const double s2 = r[0] * r[0] + r[1] * r[1];
+            double rho, w;
+            pnp_huber(s2, A.huber_delta, &rho, &w);
+            acc[27] += 0.5 * rho;
+            const double wr0 = w * r[0], wr1 = w * r[1];
+#pragma unroll
+            for (int a = 0; a < 6; ++a) {
+                const double w0 = w * J[0][a], w1 = w * J[1][a];
+#pragma unroll
+                for (int c = a; c < 6; ++c) acc[utri6(a, c)] += w0 * J[0][c] + w1 * J[1][c];
+                acc[21 + a] += J[0][a] * wr0 + J[1][a] * wr1;
+            }
+        }
+        {
+            const double v = wave_reduce_scatter32(acc, lane);
+            if ((lane & 1) == 0 && (lane >> 1) < kRed) S.s_red[wv][lane >> 1] = v;
+        }
+        __syncthreads();  // every wave's partials
+        if (STAMPS && pass < 12) STAMP(4 + 2 * pass);
+        ++pass;
+        if (wv == 0) {
+            // the waves in order (lane k sums value k), then lane 0's control
+            if (lane < kRed) {
+                double v = S.s_red[0][lane];
+#pragma unroll
+                for (int w = 1; w < kPnpWaves; ++w) v += S.s_red[w][lane];
+                S.s_sum[lane] = v;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            if (lane == 0) {
+                pnp_control(A, S.s_ctl, S.s_sum, S.s_pose);
+                S.s_run = S.s_ctl.run;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            if (S.s_run && lane < 24) {
+                const int c = lane / 12, e = lane % 12;
+                S.s_tcw[c][e] = tcw_entry(S.s_tcb[c], S.s_pose, e);
+            }
+        }
+        __syncthreads();  // s_run and the next pass's T_C_W
+        run = S.s_run;
+    }
+}
+
 // The whole of track_motion for one frame, run by one workgroup of kPnpThreads lanes: the body of
 // pnp_track_motion_kernel (A by value, in the kernel arguments) and of
 // pnp_track_motion_batch_kernel (A in a device table, one entry per workgroup).  CAP: the LDS
 // entries for features (feature j at entry j whatever CAP is, so CAP changes no result).
 template <int CAP>
 __device__ __forceinline__ void pnp_track_motion_body(const PnpArgs& A) {
-    __shared__ float s_mpw[3][CAP];              // the matched map point per feature
-    __shared__ float s_uv[2][CAP];               // undistorted coordinates per feature
-    __shared__ int8_t s_cam[CAP];                // feature -> camera, -1: no map point
-    __shared__ double s_red[kPnpWaves][kRed];
-    __shared__ double s_sum[kRed];
-    __shared__ double s_pose[12];                // R_BW, t_BW of the pass pose (wave 0's)
-    __shared__ double s_tcb[2][16];
-    __shared__ double s_tcw[2][12];              // T_C_W = T_C_B T_B_W per camera at the pass pose
-    __shared__ int s_nobs;
-    __shared__ int s_run;
-    __shared__ Ctl s_ctl;                        // the LM state between controls (wave 0's)
+    __shared__ LmLds<CAP> S;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     STAMP(0);
     const unsigned long long t_entry = wall_clock64();  // (kept by thread 0 for kernel_ms)
@@ -488,8 +627,8 @@ __device__ __forceinline__ void pnp_track_motion_body(const PnpArgs& A) {
     // feature j's observation goes to LDS entry j (cam -1: no map point).  Two features per lane
     // per round: both id / uv loads, then both bucket loads in flight together.
     int mine = 0;
-    if (tid == 0) s_nobs = 0;
-    if (tid < 32) s_tcb[tid >> 4][tid & 15] = A.TCB[tid >> 4][tid & 15];
+    if (tid == 0) S.s_nobs = 0;
+    if (tid < 32) S.s_tcb[tid >> 4][tid & 15] = A.TCB[tid >> 4][tid & 15];
     for (int j0 = tid; j0 < nf && fits; j0 += 2 * kPnpThreads) {
         uint64_t id[2];
         float2 q[2];
@@ -511,13 +650,13 @@ __device__ __forceinline__ void pnp_track_motion_body(const PnpArgs& A) {
             const int j = j0 + h * kPnpThreads;
             float pw[3];
             const bool hit = A.n_map > 0 && map_lookup(A, id[h], pw);
-            s_cam[j] = hit ? (int8_t)cam[h] : (int8_t)-1;
+            S.s_cam[j] = hit ? (int8_t)cam[h] : (int8_t)-1;
             if (hit) {
-                s_uv[0][j] = q[h].x;
-                s_uv[1][j] = q[h].y;
-                s_mpw[0][j] = pw[0];
-                s_mpw[1][j] = pw[1];
-                s_mpw[2][j] = pw[2];
+                S.s_uv[0][j] = q[h].x;
+                S.s_uv[1][j] = q[h].y;
+                S.s_mpw[0][j] = pw[0];
+                S.s_mpw[1][j] = pw[1];
+                S.s_mpw[2][j] = pw[2];
                 ++mine;
             }
         }
@@ -526,128 +665,32 @@ __device__ __forceinline__ void pnp_track_motion_body(const PnpArgs& A) {
     // keyframe (sliding_window.rs:506-517)
     if (wv == 0) {
         Ctl C;
-        C.it = 0;
-        C.status = LM_MAX_ITERS;
-        C.phase = 0;
-        C.lambda = A.lambda0;
-        C.nu = 2.0;
-        C.cost = 0.0;
-        C.initial_cost = 0.0;
-        C.pred = 0.0;
-        double TBW[16];
-        rigid_inverse(A.T_last, TBW);
-        C.x[0] = TBW[3];
-        C.x[1] = TBW[7];
-        C.x[2] = TBW[11];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) C.x[3 + k] = A.q0[k];  // UnitQuaternion::from_matrix(R_B_W) (host)
-        const Pose P0 = pose_from7(C.x);  // SE3::from (apex) of the initial 7-vector
-#pragma unroll
-        for (int k = 0; k < 9; ++k) C.R[k] = P0.R[k / 3][k % 3];
-        if (lane == 0) {
-#pragma unroll
-            for (int k = 0; k < 9; ++k) s_pose[k] = C.R[k];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) s_pose[9 + k] = C.x[k];
-            s_ctl = C;
-        }
+        ctl_start(A, C);
+        prior_pose(A, C.x, C.R);
+        if (lane == 0) ctl_publish(C, S.s_pose, S.s_ctl);
     }
     // per-wave total (one LDS atomic per wave instead of one per lane)
     for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
     __syncthreads();  // s_nobs = 0, s_tcb and s_pose (wave 0) before their uses
-    if (lane == 0 && mine) atomicAdd(&s_nobs, mine);
+    if (lane == 0 && mine) atomicAdd(&S.s_nobs, mine);
     if (wv == 0) {
         if (lane < 24) {  // T_C_W = T_C_B T_B_W, one entry per lane
             const int c = lane / 12, e = lane % 12;
-            const double* T = s_tcb[c];
-            if (e < 9) {
-                const int i = e / 3, j = e % 3;
-                s_tcw[c][e] = (T[4 * i] * s_pose[j] + T[4 * i + 1] * s_pose[3 + j]) + T[4 * i + 2] * s_pose[6 + j];
-            } else {
-                const int i = e - 9;
-                s_tcw[c][e] = ((T[4 * i] * s_pose[9] + T[4 * i + 1] * s_pose[10]) + T[4 * i + 2] * s_pose[11]) +
-                              T[4 * i + 3];
-            }
+            S.s_tcw[c][e] = tcw_entry(S.s_tcb[c], S.s_pose, e);
         }
     }
     STAMP(1);
     __syncthreads();  // the factor list, s_nobs and the first T_C_W
     STAMP(2);
-    const int nobs = s_nobs;
-    int run = (fits && nobs > 0) ? 1 : 0;
+    const int nobs = S.s_nobs;
+    const int run = (fits && nobs > 0) ? 1 : 0;
     if (tid == 0) {
-        s_ctl.n_obs = fits ? nobs : -1;
-        if (!run) s_ctl.status = LM_SKIPPED;  // no factor: treated as a failed optimisation
+        S.s_ctl.n_obs = fits ? nobs : -1;
+        if (!run) S.s_ctl.status = LM_SKIPPED;  // no factor: treated as a failed optimisation
     }
-    int pass = 0;
-    while (run) {
-        if (pass < 12) STAMP(3 + 2 * pass);
-        // one pass at the pose in s_tcw: H, g, cost over this lane's observations (j order)
-        double acc[32];
-#pragma unroll
-        for (int k = 0; k < 32; ++k) acc[k] = 0.0;
-#pragma unroll 1
-        for (int j = tid; j < nf; j += kPnpThreads) {
-            const int cam = s_cam[j];
-            if (cam < 0) continue;
-            const double pW[3] = {(double)s_mpw[0][j], (double)s_mpw[1][j], (double)s_mpw[2][j]};
-            const double uv[2] = {(double)s_uv[0][j], (double)s_uv[1][j]};
-            double r[2], J[2][6];
-            pnp_linearize_cw(pW, uv, s_tcw[cam], r, J);
-            const double s2 = r[0] * r[0] + r[1] * r[1];
-            double rho, w;
-            pnp_huber(s2, A.huber_delta, &rho, &w);
-            acc[27] += 0.5 * rho;
-            const double wr0 = w * r[0], wr1 = w * r[1];
-#pragma unroll
-            for (int a = 0; a < 6; ++a) {
-                const double w0 = w * J[0][a], w1 = w * J[1][a];
-#pragma unroll
-                for (int c = a; c < 6; ++c) acc[utri6(a, c)] += w0 * J[0][c] + w1 * J[1][c];
-                acc[21 + a] += J[0][a] * wr0 + J[1][a] * wr1;
-            }
-        }
-        {
-            const double v = wave_reduce_scatter32(acc, lane);
-            if ((lane & 1) == 0 && (lane >> 1) < kRed) s_red[wv][lane >> 1] = v;
-        }
-        __syncthreads();  // every wave's partials
-        if (pass < 12) STAMP(4 + 2 * pass);
-        ++pass;
-        if (wv == 0) {
-            // the waves in order (lane k sums value k), then lane 0's control
-            if (lane < kRed) {
-                double v = s_red[0][lane];
-#pragma unroll
-                for (int w = 1; w < kPnpWaves; ++w) v += s_red[w][lane];
-                s_sum[lane] = v;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            if (lane == 0) {
-                pnp_control(A, s_ctl, s_sum, s_pose);
-                s_run = s_ctl.run;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            if (s_run && lane < 24) {
-                const int c = lane / 12, e = lane % 12;
-                const double* T = s_tcb[c];
-                if (e < 9) {
-                    const int i = e / 3, j = e % 3;
-                    s_tcw[c][e] = (T[4 * i] * s_pose[j] + T[4 * i + 1] * s_pose[3 + j]) + T[4 * i + 2] * s_pose[6 + j];
-                } else {
-                    const int i = e - 9;
-                    s_tcw[c][e] = ((T[4 * i] * s_pose[9] + T[4 * i + 1] * s_pose[10]) + T[4 * i + 2] * s_pose[11]) +
-                                  T[4 * i + 3];
-                }
-            }
-        }
-        __syncthreads();  // s_run and the next pass's T_C_W
-        run = s_run;
-    }
+    lm_passes<true>(A, S, nf, run);
     STAMP(28);
-    if (tid == 0) pnp_finish(A, s_ctl, t_entry);
+    if (tid == 0) pnp_finish(A, S.s_ctl, t_entry);
     STAMP(29);
 }
 
@@ -709,13 +752,12 @@ struct Pnp {
 
     void init_robust() {
         if (rev[1]) return;
-        constexpr size_t cap = kPnpMaxFeatures;
-        rdbl.alloc(11 * cap + 12 * kRansacMaxHyp);
-        rint.alloc(3 * cap + 4 + 4 * kRansacMaxHyp);
-        rmask.alloc(cap);
+        rdbl.alloc(kRobustDbl);
+        rint.alloc(kRobustInt + 4 * kRansacMaxHyp);  // ... hyp_count, samples (3 per hypothesis)
+        rmask.alloc(kPnpMaxFeatures);
         hrobust.alloc(1);
         hrint.alloc(4 * kRansacMaxHyp);
-        hrmask.alloc(cap);
+        hrmask.alloc(kPnpMaxFeatures);
         RSVIO_HIP(hipEventCreate(&rev[0]));
         RSVIO_HIP(hipEventCreate(&rev[1]));
     }
@@ -805,29 +847,41 @@ int run_pnp(Pnp& p, const PnpArgs& A, hipStream_t stream, rsvio_motion_result* r
     return RSVIO_OK;
 }
 
+// A staged frame: [ids_l | ids_r | uv_l | uv_r] at `base`, 8 bytes per id and per coordinate pair,
+// 16 (n_l + n_r) in all.  pack_frame writes it from host arrays, packed_lists points A's lists at it.
+void pack_frame(uint8_t* base, const uint64_t* ids_l, const float* uv_l, size_t n_l, const uint64_t* ids_r,
+                const float* uv_r, size_t n_r) {
+    const size_t n = n_l + n_r;
+    if (n_l) std::memcpy(base, ids_l, 8 * n_l);
+    if (n_r) std::memcpy(base + 8 * n_l, ids_r, 8 * n_r);
+    if (n_l) std::memcpy(base + 8 * n, uv_l, 8 * n_l);
+    if (n_r) std::memcpy(base + 8 * n + 8 * n_l, uv_r, 8 * n_r);
+}
+
+void packed_lists(const uint8_t* base, size_t n_l, size_t n_r, PnpArgs& A) {
+    const size_t n = n_l + n_r;
+    A.ids[0] = base;
+    A.ids[1] = base + 8 * n_l;
+    A.id_stride = 8;
+    A.uv[0] = reinterpret_cast<const float2*>(base + 8 * n);
+    A.uv[1] = reinterpret_cast<const float2*>(base + 8 * n + 8 * n_l);
+    A.dcount = nullptr;
+    A.n[0] = (int)n_l;
+    A.n[1] = (int)n_r;
+}
+
 // A frame given as host arrays: staged and uploaded on the handle's stream, A's lists set to it
 void host_frame(Pnp& P, const uint64_t* ids_l, const float* uv_l, size_t n_l, const uint64_t* ids_r,
                 const float* uv_r, size_t n_r, PnpArgs& A) {
-    const size_t n = n_l + n_r, bytes = n * 16;
+    const size_t bytes = (n_l + n_r) * 16;
     if (P.feat.n < bytes || !P.feat.p) {
         const size_t cap = (size_t)kPnpMaxFeatures * 16;
         P.feat.alloc(cap);
         P.hfeat.alloc(cap);
     }
-    uint8_t* hb = P.hfeat.p;
-    if (n_l) std::memcpy(hb, ids_l, 8 * n_l);
-    if (n_r) std::memcpy(hb + 8 * n_l, ids_r, 8 * n_r);
-    if (n_l) std::memcpy(hb + 8 * n, uv_l, 8 * n_l);
-    if (n_r) std::memcpy(hb + 8 * n + 8 * n_l, uv_r, 8 * n_r);
-    if (n) RSVIO_HIP(hipMemcpyAsync(P.feat.p, hb, bytes, hipMemcpyHostToDevice, P.active()));
-    A.ids[0] = P.feat.p;
-    A.ids[1] = P.feat.p + 8 * n_l;
-    A.id_stride = 8;
-    A.uv[0] = reinterpret_cast<const float2*>(P.feat.p + 8 * n);
-    A.uv[1] = reinterpret_cast<const float2*>(P.feat.p + 8 * n + 8 * n_l);
-    A.dcount = nullptr;
-    A.n[0] = (int)n_l;
-    A.n[1] = (int)n_r;
+    pack_frame(P.hfeat.p, ids_l, uv_l, n_l, ids_r, uv_r, n_r);
+    if (bytes) RSVIO_HIP(hipMemcpyAsync(P.feat.p, P.hfeat.p, bytes, hipMemcpyHostToDevice, P.active()));
+    packed_lists(P.feat.p, n_l, n_r, A);
 }
 
 // The tracker's last collected frame, read in place: A's lists set to its output slot
@@ -865,36 +919,35 @@ bool ransac_cfg_ok(const rsvio_ransac_cfg* rc) {
     return rc && rc->n_hyp >= 1 && rc->n_hyp <= kRansacMaxHyp && rc->inlier_sq_error > 0.0;  // (NaN fails >)
 }
 
+// A timed section of `stream`: ev[0], what `launch` submits, ev[1], what `then` queues behind it
+// (copies back, not timed), and the one host wait -> the milliseconds between the events
+template <class Launch, class Then>
+float timed_section(hipStream_t stream, hipEvent_t (&ev)[2], Launch launch, Then then) {
+    RSVIO_HIP(hipEventRecord(ev[0], stream));
+    launch();
+    RSVIO_HIP(hipGetLastError());
+    RSVIO_HIP(hipEventRecord(ev[1], stream));
+    then();
+    RSVIO_HIP(hipStreamSynchronize(stream));
+    float ms = 0.f;
+    RSVIO_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    return ms;
+}
+
 // The three launches of pnp_robust.hpp on `stream`, then the one host wait; A holds the feature
 // lists (device pointers and counts, n_l + n_r <= kPnpMaxFeatures)
 int run_pnp_robust(Pnp& p, PnpArgs A, hipStream_t stream, const rsvio_ransac_cfg* rc, const int32_t* samples,
                    uint8_t* mask_l, uint8_t* mask_r, int32_t* hyp_count, rsvio_robust_motion_result* res) {
     p.init_robust();
-    constexpr size_t cap = kPnpMaxFeatures;
     const int n_l = A.n[0], n_r = A.n[1];
     RobustArgs RA{};
     A.out = &p.hrobust.p->motion;
     RA.P = A;
-    double* d = p.rdbl.p;
-    RA.B.w = d;
-    RA.B.uv = d + 3 * cap;
-    RA.B.pair_q = d + 5 * cap;
-    RA.B.pair_w = d + 8 * cap;
-    RA.B.hyp_pose = d + 11 * cap;
-    int* q = p.rint.p;
-    RA.B.cam = q;
-    RA.B.pos = q + cap;
-    RA.B.pair_ok = q + 2 * cap;
-    RA.B.counts = q + 3 * cap;
-    RA.B.hyp_count = q + 3 * cap + 4;
-    int* d_samples = q + 3 * cap + 4 + kRansacMaxHyp;
-    RA.B.samples = nullptr;
+    RA.B = robust_carve(p.rdbl.p, p.rint.p);
+    RA.B.hyp_count = p.rint.p + kRobustInt;
+    int* d_samples = RA.B.hyp_count + kRansacMaxHyp;
     RA.B.mask = p.rmask.p;
-    RA.n_hyp = rc->n_hyp;
-    RA.min_inliers = rc->min_inliers;
-    RA.seed = rc->seed;
-    RA.inlier_sq = rc->inlier_sq_error;
-    RA.min_depth = rc->min_depth;
+    set_ransac(RA, rc);
     RA.out = p.hrobust.p;
     if (samples) {
         std::memcpy(p.hrint.p, samples, sizeof(int32_t) * 3 * (size_t)rc->n_hyp);
@@ -902,23 +955,23 @@ int run_pnp_robust(Pnp& p, PnpArgs A, hipStream_t stream, const rsvio_ransac_cfg
                                  stream));
         RA.B.samples = d_samples;
     }
-    RSVIO_HIP(hipEventRecord(p.rev[0], stream));
-    hipLaunchKernelGGL(pnp_robust_join_kernel, dim3(1), dim3(kPnpThreads), 0, stream, RA);
-    hipLaunchKernelGGL(pnp_robust_score_kernel, dim3(rc->n_hyp), dim3(64), 0, stream, RA);
-    hipLaunchKernelGGL(pnp_robust_refit_kernel, dim3(1), dim3(kPnpThreads), 0, stream, RA);
-    RSVIO_HIP(hipGetLastError());
-    RSVIO_HIP(hipEventRecord(p.rev[1], stream));
     int* h_counts = p.hrint.p + 3 * kRansacMaxHyp;
-    if ((mask_l || mask_r) && n_l + n_r)
-        RSVIO_HIP(hipMemcpyAsync(p.hrmask.p, p.rmask.p, (size_t)(n_l + n_r), hipMemcpyDeviceToHost, stream));
-    if (hyp_count)
-        RSVIO_HIP(hipMemcpyAsync(h_counts, RA.B.hyp_count, sizeof(int32_t) * (size_t)rc->n_hyp, hipMemcpyDeviceToHost,
-                                 stream));
-    RSVIO_HIP(hipStreamSynchronize(stream));
+    const float ms = timed_section(
+        stream, p.rev,
+        [&] {
+            hipLaunchKernelGGL(pnp_robust_join_kernel, dim3(1), dim3(kPnpThreads), 0, stream, RA);
+            hipLaunchKernelGGL(pnp_robust_score_kernel, dim3(rc->n_hyp), dim3(64), 0, stream, RA);
+            hipLaunchKernelGGL(pnp_robust_refit_kernel, dim3(1), dim3(kPnpThreads), 0, stream, RA);
+        },
+        [&] {
+            if ((mask_l || mask_r) && n_l + n_r)
+                RSVIO_HIP(hipMemcpyAsync(p.hrmask.p, p.rmask.p, (size_t)(n_l + n_r), hipMemcpyDeviceToHost, stream));
+            if (hyp_count)
+                RSVIO_HIP(hipMemcpyAsync(h_counts, RA.B.hyp_count, sizeof(int32_t) * (size_t)rc->n_hyp,
+                                         hipMemcpyDeviceToHost, stream));
+        });
     *res = *p.hrobust.p;
     keyframe_rule(A, &res->motion);
-    float ms = 0.f;
-    RSVIO_HIP(hipEventElapsedTime(&ms, p.rev[0], p.rev[1]));
     res->device_ms = ms;
     if (mask_l && n_l) std::memcpy(mask_l, p.hrmask.p, (size_t)n_l);
     if (mask_r && n_r) std::memcpy(mask_r, p.hrmask.p + n_l, (size_t)n_r);
@@ -1002,10 +1055,8 @@ struct PnpBatch {
     HostBuf<int> hcount;
     HostBuf<uint8_t> hmask;
     HostBuf<CovOut> hcov;              // the covariance kernel's result table
-    double device_ms = 0.0;
 
-    static constexpr size_t kDblPerStream = 11 * (size_t)kPnpMaxFeatures + 12 * (size_t)kRansacMaxHyp;
-    static constexpr size_t kIntPerStream = 3 * (size_t)kPnpMaxFeatures + 4;
+    static constexpr size_t kDblPerStream = kRobustDbl, kIntPerStream = kRobustInt;
 
     void init(int dev, std::vector<Pnp*> handles) {
         device = dev;
@@ -1040,14 +1091,18 @@ struct PnpBatch {
     }
 };
 
-// The host-side checks of a batched call: nothing is launched or written unless all pass
-int batch_check(const PnpBatch& b, const rsvio_motion_frame* frames, const rsvio_lm_cfg* cfg, const char* who) {
+// The host-side checks of a batched call `who`: nothing is launched or written unless all pass.
+// lm: a tracking call, whose slots need T_W_B_last_kf and a cfg (their own or the call's `cfg`);
+// the covariance call reads neither
+int batch_check(const PnpBatch& b, const rsvio_motion_frame* frames, const char* who, bool lm,
+                const rsvio_lm_cfg* cfg = nullptr) {
     for (int i = 0; i < b.n; ++i) {
         const rsvio_motion_frame& f = frames[i];
-        if (!f.T_W_B_last_kf || !f.T_C_B2 || (!f.cfg && !cfg) || (f.n_l && (!f.ids_l || !f.uv_l)) ||
+        if ((lm && (!f.T_W_B_last_kf || (!f.cfg && !cfg))) || !f.T_C_B2 || (f.n_l && (!f.ids_l || !f.uv_l)) ||
             (f.n_r && (!f.ids_r || !f.uv_r)) || f.id_stride < 0 || (f.id_stride && f.id_stride < 8)) {
             char msg[96];
-            std::snprintf(msg, sizeof msg, "%s: slot %d: a NULL argument, no cfg or a bad id_stride", who, i);
+            std::snprintf(msg, sizeof msg, "%s: slot %d: a NULL argument%s or a bad id_stride", who, i,
+                          lm ? ", no cfg" : "");
             set_last_error(msg);
             return RSVIO_ERR_INVALID_ARG;
         }
@@ -1073,6 +1128,23 @@ int batch_cap(const PnpBatch& b, const rsvio_motion_frame* frames) {
     return most <= (size_t)kPnpBatchSmallCap ? kPnpBatchSmallCap : kPnpMaxFeatures;
 }
 
+// f(std::integral_constant<int, CAP>) for batch_cap's value: a kernel<CAP> has one launch site
+template <class F>
+void with_cap(int cap, F f) {
+    if (cap == kPnpBatchSmallCap)
+        f(std::integral_constant<int, kPnpBatchSmallCap>{});
+    else
+        f(std::integral_constant<int, kPnpMaxFeatures>{});
+}
+
+// A batched run's timed section on the batch's stream and events; the time also to *device_ms
+template <class Launch, class Then = void (*)()>
+float batch_timed(PnpBatch& b, double* device_ms, Launch launch, Then then = [] {}) {
+    const float ms = timed_section(b.stream, b.ev, launch, then);
+    if (device_ms) *device_ms = ms;
+    return ms;
+}
+
 // Lay the call's image out (table of n entries of `entry` bytes, host frames, samples of
 // `samp_bytes` each where given, then `extra` bytes the caller fills) and stage the host frames and
 // samples; returns the size without the extra bytes, i.e. their offset
@@ -1088,14 +1160,7 @@ size_t batch_stage(PnpBatch& b, const rsvio_motion_frame* frames, size_t entry, 
     b.reserve_image(off + extra);
     for (int i = 0; i < b.n; ++i) {
         const rsvio_motion_frame& f = frames[i];
-        if (!f.on_device) {
-            uint8_t* hb = b.himg.p + b.frame_off[i];
-            const size_t n = f.n_l + f.n_r;
-            if (f.n_l) std::memcpy(hb, f.ids_l, 8 * f.n_l);
-            if (f.n_r) std::memcpy(hb + 8 * f.n_l, f.ids_r, 8 * f.n_r);
-            if (f.n_l) std::memcpy(hb + 8 * n, f.uv_l, 8 * f.n_l);
-            if (f.n_r) std::memcpy(hb + 8 * n + 8 * f.n_l, f.uv_r, 8 * f.n_r);
-        }
+        if (!f.on_device) pack_frame(b.himg.p + b.frame_off[i], f.ids_l, f.uv_l, f.n_l, f.ids_r, f.uv_r, f.n_r);
         if (samp_bytes && f.samples) std::memcpy(b.himg.p + b.samp_off[i], f.samples, samp_bytes);
     }
     return off;
@@ -1103,24 +1168,14 @@ size_t batch_stage(PnpBatch& b, const rsvio_motion_frame* frames, size_t entry, 
 
 // Slot i's lists in A: device pointers read in place, or the frame staged in the call's image
 void batch_lists(const PnpBatch& b, int i, const rsvio_motion_frame& f, PnpArgs& A) {
+    packed_lists(b.dimg.p + b.frame_off[i], f.n_l, f.n_r, A);
     if (f.on_device) {  // device pointers, read in place
         A.ids[0] = reinterpret_cast<const uint8_t*>(f.ids_l);
         A.ids[1] = reinterpret_cast<const uint8_t*>(f.ids_r);
         A.id_stride = f.id_stride ? f.id_stride : 8;
         A.uv[0] = reinterpret_cast<const float2*>(f.uv_l);
         A.uv[1] = reinterpret_cast<const float2*>(f.uv_r);
-    } else {
-        const uint8_t* d = b.dimg.p + b.frame_off[i];
-        const size_t n = f.n_l + f.n_r;
-        A.ids[0] = d;
-        A.ids[1] = d + 8 * f.n_l;
-        A.id_stride = 8;
-        A.uv[0] = reinterpret_cast<const float2*>(d + 8 * n);
-        A.uv[1] = reinterpret_cast<const float2*>(d + 8 * n + 8 * f.n_l);
     }
-    A.dcount = nullptr;
-    A.n[0] = (int)f.n_l;
-    A.n[1] = (int)f.n_r;
 }
 
 // Slot i's PnpArgs: handle i's current map, frame i's poses, cfg and lists
@@ -1143,20 +1198,14 @@ int run_pnp_batch(PnpBatch& b, const rsvio_motion_frame* frames, const rsvio_lm_
     }
     RSVIO_HIP(hipMemcpyAsync(b.dimg.p, b.himg.p, bytes, hipMemcpyHostToDevice, b.stream));
     const PnpArgs* dtab = reinterpret_cast<const PnpArgs*>(b.dimg.p);
-    RSVIO_HIP(hipEventRecord(b.ev[0], b.stream));
-    if (cap == kPnpBatchSmallCap)
-        hipLaunchKernelGGL(pnp_track_motion_batch_kernel<kPnpBatchSmallCap>, dim3(b.n), dim3(kPnpThreads), 0,
-                           b.stream, dtab);
-    else
-        hipLaunchKernelGGL(pnp_track_motion_batch_kernel<kPnpMaxFeatures>, dim3(b.n), dim3(kPnpThreads), 0, b.stream,
-                           dtab);
-    RSVIO_HIP(hipGetLastError());
-    RSVIO_HIP(hipEventRecord(b.ev[1], b.stream));
-    RSVIO_HIP(hipStreamSynchronize(b.stream));
-    float ms = 0.f;
-    RSVIO_HIP(hipEventElapsedTime(&ms, b.ev[0], b.ev[1]));
-    b.device_ms = ms;
-    if (device_ms) *device_ms = ms;
+    batch_timed(
+        b, device_ms,
+        [&] {
+            with_cap(cap, [&](auto c) {
+                hipLaunchKernelGGL(pnp_track_motion_batch_kernel<decltype(c)::value>, dim3(b.n), dim3(kPnpThreads), 0,
+                                   b.stream, dtab);
+            });
+        });
     for (int i = 0; i < b.n; ++i) {
         results[i] = b.hres.p[i];
         keyframe_rule(tab[i], &results[i]);
@@ -1169,7 +1218,6 @@ int run_pnp_batch_robust(PnpBatch& b, const rsvio_motion_frame* frames, const rs
                          rsvio_robust_motion_result* results, double* device_ms) {
     RSVIO_HIP(hipSetDevice(b.device));
     b.init_robust();
-    constexpr size_t fcap = kPnpMaxFeatures;
     const int cap = batch_cap(b, frames);
     const size_t n_hyp = (size_t)rc->n_hyp;
     const size_t bytes = batch_stage(b, frames, sizeof(RobustArgs), sizeof(int32_t) * 3 * n_hyp);
@@ -1186,25 +1234,11 @@ int run_pnp_batch_robust(PnpBatch& b, const rsvio_motion_frame* frames, const rs
         RobustArgs RA{};
         RA.P = batch_args(b, i, frames[i], cfg, rule);
         RA.P.out = &b.hrobust.p[i].motion;
-        double* d = b.rdbl.p + PnpBatch::kDblPerStream * i;
-        RA.B.w = d;
-        RA.B.uv = d + 3 * fcap;
-        RA.B.pair_q = d + 5 * fcap;
-        RA.B.pair_w = d + 8 * fcap;
-        RA.B.hyp_pose = d + 11 * fcap;
-        int* q = b.rint.p + PnpBatch::kIntPerStream * i;
-        RA.B.cam = q;
-        RA.B.pos = q + fcap;
-        RA.B.pair_ok = q + 2 * fcap;
-        RA.B.counts = q + 3 * fcap;
+        RA.B = robust_carve(b.rdbl.p + PnpBatch::kDblPerStream * i, b.rint.p + PnpBatch::kIntPerStream * i);
         RA.B.hyp_count = b.rcount.p + n_hyp * i;
         RA.B.samples = frames[i].samples ? reinterpret_cast<const int*>(b.dimg.p + b.samp_off[i]) : nullptr;
         RA.B.mask = b.rmask.p + mstride * i;
-        RA.n_hyp = rc->n_hyp;
-        RA.min_inliers = rc->min_inliers;
-        RA.seed = rc->seed;
-        RA.inlier_sq = rc->inlier_sq_error;
-        RA.min_depth = rc->min_depth;
+        set_ransac(RA, rc);
         RA.out = b.hrobust.p + i;
         tab[i] = RA;
     }
@@ -1212,32 +1246,23 @@ int run_pnp_batch_robust(PnpBatch& b, const rsvio_motion_frame* frames, const rs
     if (want_count && b.hcount.n < n_hyp * b.n) b.hcount.alloc(n_hyp * b.n);
     RSVIO_HIP(hipMemcpyAsync(b.dimg.p, b.himg.p, bytes, hipMemcpyHostToDevice, b.stream));
     const RobustArgs* dtab = reinterpret_cast<const RobustArgs*>(b.dimg.p);
-    RSVIO_HIP(hipEventRecord(b.ev[0], b.stream));
-    if (cap == kPnpBatchSmallCap) {
-        hipLaunchKernelGGL(pnp_robust_join_batch_kernel<kPnpBatchSmallCap>, dim3(b.n), dim3(kPnpThreads), 0, b.stream,
-                           dtab);
-        hipLaunchKernelGGL(pnp_robust_score_batch_kernel, dim3(rc->n_hyp, b.n), dim3(64), 0, b.stream, dtab);
-        hipLaunchKernelGGL(pnp_robust_refit_batch_kernel<kPnpBatchSmallCap>, dim3(b.n), dim3(kPnpThreads), 0, b.stream,
-                           dtab);
-    } else {
-        hipLaunchKernelGGL(pnp_robust_join_batch_kernel<kPnpMaxFeatures>, dim3(b.n), dim3(kPnpThreads), 0, b.stream,
-                           dtab);
-        hipLaunchKernelGGL(pnp_robust_score_batch_kernel, dim3(rc->n_hyp, b.n), dim3(64), 0, b.stream, dtab);
-        hipLaunchKernelGGL(pnp_robust_refit_batch_kernel<kPnpMaxFeatures>, dim3(b.n), dim3(kPnpThreads), 0, b.stream,
-                           dtab);
-    }
-    RSVIO_HIP(hipGetLastError());
-    RSVIO_HIP(hipEventRecord(b.ev[1], b.stream));
-    if (want_mask && mstride)
-        RSVIO_HIP(hipMemcpyAsync(b.hmask.p, b.rmask.p, mstride * b.n, hipMemcpyDeviceToHost, b.stream));
-    if (want_count)
-        RSVIO_HIP(hipMemcpyAsync(b.hcount.p, b.rcount.p, sizeof(int32_t) * n_hyp * b.n, hipMemcpyDeviceToHost,
-                                 b.stream));
-    RSVIO_HIP(hipStreamSynchronize(b.stream));
-    float ms = 0.f;
-    RSVIO_HIP(hipEventElapsedTime(&ms, b.ev[0], b.ev[1]));
-    b.device_ms = ms;
-    if (device_ms) *device_ms = ms;
+    const float ms = batch_timed(
+        b, device_ms,
+        [&] {
+            with_cap(cap, [&](auto c) {
+                constexpr int CAP = decltype(c)::value;
+                hipLaunchKernelGGL(pnp_robust_join_batch_kernel<CAP>, dim3(b.n), dim3(kPnpThreads), 0, b.stream, dtab);
+                hipLaunchKernelGGL(pnp_robust_score_batch_kernel, dim3(rc->n_hyp, b.n), dim3(64), 0, b.stream, dtab);
+                hipLaunchKernelGGL(pnp_robust_refit_batch_kernel<CAP>, dim3(b.n), dim3(kPnpThreads), 0, b.stream, dtab);
+            });
+        },
+        [&] {
+            if (want_mask && mstride)
+                RSVIO_HIP(hipMemcpyAsync(b.hmask.p, b.rmask.p, mstride * b.n, hipMemcpyDeviceToHost, b.stream));
+            if (want_count)
+                RSVIO_HIP(hipMemcpyAsync(b.hcount.p, b.rcount.p, sizeof(int32_t) * n_hyp * b.n, hipMemcpyDeviceToHost,
+                                         b.stream));
+        });
     for (int i = 0; i < b.n; ++i) {
         const rsvio_motion_frame& f = frames[i];
         results[i] = b.hrobust.p[i];
@@ -1248,30 +1273,6 @@ int run_pnp_batch_robust(PnpBatch& b, const rsvio_motion_frame* frames, const rs
         if (f.mask_r && f.n_r) std::memcpy(f.mask_r, m + f.n_l, f.n_r);
         if (f.hyp_count) std::memcpy(f.hyp_count, b.hcount.p + n_hyp * i, sizeof(int32_t) * n_hyp);
     }
-    return RSVIO_OK;
-}
-
-// The host-side checks of the batched covariance call (it reads no cfg and no T_W_B_last_kf)
-int batch_cov_check(const PnpBatch& b, const rsvio_motion_frame* frames) {
-    for (int i = 0; i < b.n; ++i) {
-        const rsvio_motion_frame& f = frames[i];
-        if (!f.T_C_B2 || (f.n_l && (!f.ids_l || !f.uv_l)) || (f.n_r && (!f.ids_r || !f.uv_r)) || f.id_stride < 0 ||
-            (f.id_stride && f.id_stride < 8)) {
-            char msg[96];
-            std::snprintf(msg, sizeof msg, "rsvio_pnp_batch_covariance: slot %d: a NULL argument or a bad id_stride", i);
-            set_last_error(msg);
-            return RSVIO_ERR_INVALID_ARG;
-        }
-    }
-    for (int i = 0; i < b.n; ++i)
-        if (frames[i].n_l > (size_t)kPnpMaxFeatures || frames[i].n_r > (size_t)kPnpMaxFeatures ||
-            frames[i].n_l + frames[i].n_r > (size_t)kPnpMaxFeatures) {
-            char msg[96];
-            std::snprintf(msg, sizeof msg, "rsvio_pnp_batch_covariance: slot %d: more than 4096 features in one frame",
-                          i);
-            set_last_error(msg);
-            return RSVIO_ERR_CAPACITY;
-        }
     return RSVIO_OK;
 }
 
@@ -1301,16 +1302,12 @@ int run_pnp_batch_cov(PnpBatch& b, const rsvio_motion_frame* frames, const doubl
         tab[i] = A;
     }
     RSVIO_HIP(hipMemcpyAsync(b.dimg.p, b.himg.p, moff + mbytes, hipMemcpyHostToDevice, b.stream));
-    RSVIO_HIP(hipEventRecord(b.ev[0], b.stream));
-    hipLaunchKernelGGL(pnp_covariance_batch_kernel, dim3(b.n), dim3(kPnpThreads), 0, b.stream,
-                       reinterpret_cast<const CovArgs*>(b.dimg.p));
-    RSVIO_HIP(hipGetLastError());
-    RSVIO_HIP(hipEventRecord(b.ev[1], b.stream));
-    RSVIO_HIP(hipStreamSynchronize(b.stream));
-    float ms = 0.f;
-    RSVIO_HIP(hipEventElapsedTime(&ms, b.ev[0], b.ev[1]));
-    b.device_ms = ms;
-    if (device_ms) *device_ms = ms;
+    batch_timed(
+        b, device_ms,
+        [&] {
+            hipLaunchKernelGGL(pnp_covariance_batch_kernel, dim3(b.n), dim3(kPnpThreads), 0, b.stream,
+                               reinterpret_cast<const CovArgs*>(b.dimg.p));
+        });
     for (int i = 0; i < b.n; ++i) {
         std::memcpy(cov + 36 * (size_t)i, b.hcov.p[i].cov, sizeof b.hcov.p[i].cov);
         info[i] = b.hcov.p[i].info;
@@ -1519,7 +1516,7 @@ void rsvio_pnp_batch_destroy(rsvio_pnp_batch* b) { delete b; }
 int rsvio_pnp_batch_track_motion(rsvio_pnp_batch* b, const rsvio_motion_frame* frames, const rsvio_lm_cfg* cfg,
                                  const rsvio_keyframe_rule* rule, rsvio_motion_result* results, double* device_ms) {
     if (!b || !frames || !rule || !results) return RSVIO_ERR_INVALID_ARG;
-    const int rc = rsvio::batch_check(b->b, frames, cfg, "rsvio_pnp_batch_track_motion");
+    const int rc = rsvio::batch_check(b->b, frames, "rsvio_pnp_batch_track_motion", true, cfg);
     if (rc != RSVIO_OK) return rc;
     return guarded([&] { return rsvio::run_pnp_batch(b->b, frames, cfg, rule, results, device_ms); });
 }
@@ -1528,7 +1525,7 @@ int rsvio_pnp_batch_track_motion_robust(rsvio_pnp_batch* b, const rsvio_motion_f
                                         const rsvio_keyframe_rule* rule, const rsvio_ransac_cfg* ransac,
                                         rsvio_robust_motion_result* results, double* device_ms) {
     if (!b || !frames || !rule || !results || !rsvio::ransac_cfg_ok(ransac)) return RSVIO_ERR_INVALID_ARG;
-    const int rc = rsvio::batch_check(b->b, frames, cfg, "rsvio_pnp_batch_track_motion_robust");
+    const int rc = rsvio::batch_check(b->b, frames, "rsvio_pnp_batch_track_motion_robust", true, cfg);
     if (rc != RSVIO_OK) return rc;
     return guarded(
         [&] { return rsvio::run_pnp_batch_robust(b->b, frames, cfg, rule, ransac, results, device_ms); });
@@ -1571,7 +1568,7 @@ int rsvio_motion_covariance_tracker(rsvio_pnp* h, rsvio_tracker* t, const uint8_
 int rsvio_pnp_batch_covariance(rsvio_pnp_batch* b, const rsvio_motion_frame* frames, const double* T_W_B,
                                double huber_delta, double* cov, rsvio_motion_cov_info* info, double* device_ms) {
     if (!b || !frames || !T_W_B || !cov || !info || !(huber_delta > 0.0)) return RSVIO_ERR_INVALID_ARG;
-    const int rc = rsvio::batch_cov_check(b->b, frames);
+    const int rc = rsvio::batch_check(b->b, frames, "rsvio_pnp_batch_covariance", false);
     if (rc != RSVIO_OK) return rc;
     return guarded([&] { return rsvio::run_pnp_batch_cov(b->b, frames, T_W_B, huber_delta, cov, info, device_ms); });
 }

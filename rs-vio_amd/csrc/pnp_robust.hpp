@@ -1,7 +1,8 @@
 // pnp_robust.hpp -- outlier-robust motion tracking: a stereo 3-point RANSAC in front of the PnP LM
 // (rsvio_track_motion_robust*).  Included by pnp.hip inside its file-local namespace, after
-// pnp_track_motion_kernel: it reuses that file's PnpArgs, map_lookup, pnp_linearize_cw, pnp_huber,
-// pnp_control and pnp_finish, and leaves the plain kernel as it is.
+// pnp_track_motion_kernel: it reuses that file's PnpArgs, map_lookup and pnp_finish, and its refit
+// runs that file's LM -- LmLds, prior_pose, ctl_start, ctl_publish, tcw_entry and lm_passes, the one
+// pass loop there is -- so the two cannot drift apart.
 //
 // Three launches on the handle's stream, no host wait between them and no workgroup waiting on
 // another (no spin flag, no last-block reducer): what one launch reduces, the next one reads.
@@ -14,9 +15,9 @@
 //      starts from), h >= 1 the rigid motion between a world and a body triangle of three pairs;
 //      the inliers over all joined observations by ballot / popcount (integers: order-free).
 //   R3 pnp_robust_refit_kernel   one workgroup: the winner (largest count, lowest h on a tie),
-//      the plain kernel's LM on the winner's inliers from the winner's pose -- the same factor
-//      order, the same lane <-> feature assignment and reduction order, so n_hyp = 1 with an
-//      all-accepting threshold gives the plain kernel's bits -- then the inlier / outlier mask
+//      the plain kernel's LM (lm_passes) on the winner's inliers from the winner's pose -- the
+//      same function over the same factor order and lane <-> feature assignment, so n_hyp = 1 with
+//      an all-accepting threshold gives the plain kernel's bits -- then the inlier / outlier mask
 //      of every joined observation at the refined pose.
 #pragma once
 
@@ -46,6 +47,35 @@ struct RobustArgs {
     rsvio_robust_motion_result* out;  // pinned host memory
 };
 
+// One stream's scratch as the host allocates it: RobustBufs' f64 arrays in one buffer (w, uv,
+// pair_q, pair_w, hyp_pose), cam, pos, pair_ok and counts (4) in another; hyp_count, samples and
+// mask are placed by the caller
+constexpr size_t kRobustDbl = (3 + 2 + 3 + 3) * (size_t)kPnpMaxFeatures + 12 * (size_t)kRansacMaxHyp;
+constexpr size_t kRobustInt = 3 * (size_t)kPnpMaxFeatures + 4;
+
+RobustBufs robust_carve(double* d, int* q) {
+    constexpr size_t cap = kPnpMaxFeatures;
+    RobustBufs B{};
+    B.w = d;
+    B.uv = B.w + 3 * cap;
+    B.pair_q = B.uv + 2 * cap;
+    B.pair_w = B.pair_q + 3 * cap;
+    B.hyp_pose = B.pair_w + 3 * cap;
+    B.cam = q;
+    B.pos = B.cam + cap;
+    B.pair_ok = B.pos + cap;
+    B.counts = B.pair_ok + cap;
+    return B;
+}
+
+void set_ransac(RobustArgs& RA, const rsvio_ransac_cfg* rc) {
+    RA.n_hyp = rc->n_hyp;
+    RA.min_inliers = rc->min_inliers;
+    RA.seed = rc->seed;
+    RA.inlier_sq = rc->inlier_sq_error;
+    RA.min_depth = rc->min_depth;
+}
+
 __host__ __device__ __forceinline__ uint64_t splitmix64_at(uint64_t seed, uint64_t i) {
     uint64_t z = seed + 0x9E3779B97F4A7C15ull * (i + 1ull);
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -53,7 +83,8 @@ __host__ __device__ __forceinline__ uint64_t splitmix64_at(uint64_t seed, uint64
     return z ^ (z >> 31);
 }
 
-// T_C_W = T_C_B [R | t] as 12 values (R row-major, then t): the plain kernel's s_tcw
+// T_C_W = T_C_B [R | t] as 12 values (R row-major, then t) by one thread, R and t apart: pnp.hip's
+// tcw_entry for all 12 entries (written out: through tcw_entry R2's schedule changes)
 __device__ __forceinline__ void compose_tcw(const double* T, const double* R, const double* t, double* out) {
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
@@ -324,20 +355,6 @@ __device__ __forceinline__ bool triangle_frame(const double p[3][3], double F[9]
     return true;
 }
 
-// The prior: the pose7 the plain kernel starts from, its rotation and translation
-__device__ __forceinline__ void prior_pose(const PnpArgs& A, double x[7], double R[9]) {
-    double TBW[16];
-    rigid_inverse(A.T_last, TBW);
-    x[0] = TBW[3];
-    x[1] = TBW[7];
-    x[2] = TBW[11];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) x[3 + k] = A.q0[k];
-    const Pose P0 = pose_from7(x);
-#pragma unroll
-    for (int k = 0; k < 9; ++k) R[k] = P0.R[k / 3][k % 3];
-}
-
 // R2: one wave per hypothesis (blockIdx.x)
 __device__ __forceinline__ void pnp_robust_score_body(const RobustArgs& RA) {
     const PnpArgs& A = RA.P;
@@ -454,26 +471,17 @@ __device__ __forceinline__ void quat_of_rotation(const double* R, double* q) {
     }
 }
 
-// R3: select, refit, classify.  One workgroup; the LM section is pnp_track_motion_kernel's, pass
-// for pass, over the LDS entries of the winner's inliers.
+// R3: select, refit, classify.  One workgroup; the LM is the plain kernel's (ctl_start,
+// ctl_publish, tcw_entry and lm_passes of pnp.hip, without the stamps) over the LDS entries of the
+// winner's inliers: a feature that is no inlier, or has no map point, is no factor.
 template <int CAP>
 __device__ __forceinline__ void pnp_robust_refit_body(const RobustArgs& RA) {
-    __shared__ float s_mpw[3][CAP];
-    __shared__ float s_uv[2][CAP];
-    __shared__ int8_t s_cam[CAP];                 // feature -> camera, -1: no factor (no map point or outlier)
+    __shared__ LmLds<CAP> S;
     __shared__ uint8_t s_mask[CAP];
-    __shared__ double s_red[kPnpWaves][kRed];
-    __shared__ double s_sum[kRed];
-    __shared__ double s_pose[12];
-    __shared__ double s_tcb[2][16];
-    __shared__ double s_tcw[2][12];
     __shared__ double s_tcw0[2][12];              // T_C_W at the winner's pose
     __shared__ long long s_key[kPnpWaves];
     __shared__ int s_nvalid[kPnpWaves];
-    __shared__ int s_nobs;
     __shared__ int s_nin;
-    __shared__ int s_run;
-    __shared__ Ctl s_ctl;
     const PnpArgs& A = RA.P;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     constexpr int cap = kPnpMaxFeatures;
@@ -500,12 +508,12 @@ __device__ __forceinline__ void pnp_robust_refit_body(const RobustArgs& RA) {
         s_nvalid[wv] = nvalid;
     }
     if (tid == 0) {
-        s_nobs = 0;
+        S.s_nobs = 0;
         s_nin = 0;
     }
-    if (tid < 32) s_tcb[tid >> 4][tid & 15] = A.TCB[tid >> 4][tid & 15];
+    if (tid < 32) S.s_tcb[tid >> 4][tid & 15] = A.TCB[tid >> 4][tid & 15];
     for (int j = tid; j < CAP; j += kPnpThreads) {
-        s_cam[j] = -1;
+        S.s_cam[j] = -1;
         s_mask[j] = 0;
     }
     __syncthreads();
@@ -523,14 +531,7 @@ __device__ __forceinline__ void pnp_robust_refit_body(const RobustArgs& RA) {
     // wave 0: the LM state, F starting from the winner's pose (h = 0: the plain kernel's start)
     if (wv == 0) {
         Ctl C;
-        C.it = 0;
-        C.status = LM_MAX_ITERS;
-        C.phase = 0;
-        C.lambda = A.lambda0;
-        C.nu = 2.0;
-        C.cost = 0.0;
-        C.initial_cost = 0.0;
-        C.pred = 0.0;
+        ctl_start(A, C);
         if (best_h <= 0) {
             prior_pose(A, C.x, C.R);
         } else {
@@ -545,27 +546,13 @@ __device__ __forceinline__ void pnp_robust_refit_body(const RobustArgs& RA) {
 #pragma unroll
             for (int k = 0; k < 9; ++k) C.R[k] = P0.R[k / 3][k % 3];
         }
-        if (lane == 0) {
-#pragma unroll
-            for (int k = 0; k < 9; ++k) s_pose[k] = C.R[k];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) s_pose[9 + k] = C.x[k];
-            s_ctl = C;
-        }
+        if (lane == 0) ctl_publish(C, S.s_pose, S.s_ctl);
     }
     __syncthreads();  // s_tcb, s_pose
     if (wv == 0 && lane < 24) {
         const int c = lane / 12, e = lane % 12;
-        const double* T = s_tcb[c];
-        double v;
-        if (e < 9) {
-            const int i = e / 3, j = e % 3;
-            v = (T[4 * i] * s_pose[j] + T[4 * i + 1] * s_pose[3 + j]) + T[4 * i + 2] * s_pose[6 + j];
-        } else {
-            const int i = e - 9;
-            v = ((T[4 * i] * s_pose[9] + T[4 * i + 1] * s_pose[10]) + T[4 * i + 2] * s_pose[11]) + T[4 * i + 3];
-        }
-        s_tcw[c][e] = v;
+        const double v = tcw_entry(S.s_tcb[c], S.s_pose, e);
+        S.s_tcw[c][e] = v;
         s_tcw0[c][e] = v;
     }
     __syncthreads();  // the winner's T_C_W
@@ -577,110 +564,39 @@ __device__ __forceinline__ void pnp_robust_refit_body(const RobustArgs& RA) {
         const int cam = RA.B.cam[k];
         if (!robust_inlier(s_tcw0[0], s_tcw0[1], cam, w, uv, RA.min_depth, RA.inlier_sq)) continue;
         const int j = cam == 0 ? RA.B.pos[k] : n0 + RA.B.pos[k];
-        s_cam[j] = (int8_t)cam;
-        s_uv[0][j] = (float)uv[0];
-        s_uv[1][j] = (float)uv[1];
-        s_mpw[0][j] = (float)w[0];
-        s_mpw[1][j] = (float)w[1];
-        s_mpw[2][j] = (float)w[2];
+        S.s_cam[j] = (int8_t)cam;
+        S.s_uv[0][j] = (float)uv[0];
+        S.s_uv[1][j] = (float)uv[1];
+        S.s_mpw[0][j] = (float)w[0];
+        S.s_mpw[1][j] = (float)w[1];
+        S.s_mpw[2][j] = (float)w[2];
         ++mine;
     }
     for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
-    if (lane == 0 && mine) atomicAdd(&s_nobs, mine);
+    if (lane == 0 && mine) atomicAdd(&S.s_nobs, mine);
     __syncthreads();  // the factor list and s_nobs
-    const int nobs = s_nobs;
-    int run = (consensus && nobs > 0) ? 1 : 0;
+    const int nobs = S.s_nobs;
+    const int run = (consensus && nobs > 0) ? 1 : 0;
     if (tid == 0) {
-        s_ctl.n_obs = run ? nobs : 0;
-        if (!run) s_ctl.status = LM_SKIPPED;
+        S.s_ctl.n_obs = run ? nobs : 0;
+        if (!run) S.s_ctl.status = LM_SKIPPED;
     }
-    while (run) {
-        double acc[32];
-#pragma unroll
-        for (int k = 0; k < 32; ++k) acc[k] = 0.0;
-#pragma unroll 1
-        for (int j = tid; j < nf; j += kPnpThreads) {
-            const int cam = s_cam[j];
-            if (cam < 0) continue;
-            const double pW[3] = {(double)s_mpw[0][j], (double)s_mpw[1][j], (double)s_mpw[2][j]};
-            const double uv[2] = {(double)s_uv[0][j], (double)s_uv[1][j]};
-            double r[2], J[2][6];
-            pnp_linearize_cw(pW, uv, s_tcw[cam], r, J);
-            const double s2 = r[0] * r[0] + r[1] * r[1];
-            double rho, w;
-            pnp_huber(s2, A.huber_delta, &rho, &w);
-            acc[27] += 0.5 * rho;
-            const double wr0 = w * r[0], wr1 = w * r[1];
-#pragma unroll
-            for (int a = 0; a < 6; ++a) {
-                const double w0 = w * J[0][a], w1 = w * J[1][a];
-#pragma unroll
-                for (int c = a; c < 6; ++c) acc[utri6(a, c)] += w0 * J[0][c] + w1 * J[1][c];
-                acc[21 + a] += J[0][a] * wr0 + J[1][a] * wr1;
-            }
-        }
-        {
-            const double v = wave_reduce_scatter32(acc, lane);
-            if ((lane & 1) == 0 && (lane >> 1) < kRed) s_red[wv][lane >> 1] = v;
-        }
-        __syncthreads();  // every wave's partials
-        if (wv == 0) {
-            if (lane < kRed) {
-                double v = s_red[0][lane];
-#pragma unroll
-                for (int w = 1; w < kPnpWaves; ++w) v += s_red[w][lane];
-                s_sum[lane] = v;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            if (lane == 0) {
-                pnp_control(A, s_ctl, s_sum, s_pose);
-                s_run = s_ctl.run;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            if (s_run && lane < 24) {
-                const int c = lane / 12, e = lane % 12;
-                const double* T = s_tcb[c];
-                if (e < 9) {
-                    const int i = e / 3, j = e % 3;
-                    s_tcw[c][e] = (T[4 * i] * s_pose[j] + T[4 * i + 1] * s_pose[3 + j]) + T[4 * i + 2] * s_pose[6 + j];
-                } else {
-                    const int i = e - 9;
-                    s_tcw[c][e] = ((T[4 * i] * s_pose[9] + T[4 * i + 1] * s_pose[10]) + T[4 * i + 2] * s_pose[11]) +
-                                  T[4 * i + 3];
-                }
-            }
-        }
-        __syncthreads();  // s_run and the next pass's T_C_W
-        run = s_run;
-    }
+    lm_passes<false>(A, S, nf, run);
     // the mask at the refined pose (a failed LM: at the winner's); without consensus every joined
     // observation is an outlier
     __syncthreads();
-    const bool refined = s_ctl.status > 0;
+    const bool refined = S.s_ctl.status > 0;
     if (tid == 0 && refined) {
-        const Pose P = pose_from7(s_ctl.x);
+        const Pose P = pose_from7(S.s_ctl.x);
 #pragma unroll
-        for (int k = 0; k < 9; ++k) s_pose[k] = P.R[k / 3][k % 3];
+        for (int k = 0; k < 9; ++k) S.s_pose[k] = P.R[k / 3][k % 3];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) s_pose[9 + k] = s_ctl.x[k];
+        for (int k = 0; k < 3; ++k) S.s_pose[9 + k] = S.s_ctl.x[k];
     }
     __syncthreads();
     if (tid < 24) {
         const int c = tid / 12, e = tid % 12;
-        const double* T = s_tcb[c];
-        double v = s_tcw0[c][e];
-        if (refined) {
-            if (e < 9) {
-                const int i = e / 3, j = e % 3;
-                v = (T[4 * i] * s_pose[j] + T[4 * i + 1] * s_pose[3 + j]) + T[4 * i + 2] * s_pose[6 + j];
-            } else {
-                const int i = e - 9;
-                v = ((T[4 * i] * s_pose[9] + T[4 * i + 1] * s_pose[10]) + T[4 * i + 2] * s_pose[11]) + T[4 * i + 3];
-            }
-        }
-        s_tcw[c][e] = v;
+        S.s_tcw[c][e] = refined ? tcw_entry(S.s_tcb[c], S.s_pose, e) : s_tcw0[c][e];
     }
     __syncthreads();
     int nin = 0;
@@ -688,7 +604,7 @@ __device__ __forceinline__ void pnp_robust_refit_body(const RobustArgs& RA) {
         const double w[3] = {RA.B.w[k], RA.B.w[cap + k], RA.B.w[2 * cap + k]};
         const double uv[2] = {RA.B.uv[k], RA.B.uv[cap + k]};
         const int cam = RA.B.cam[k];
-        const bool in = consensus && robust_inlier(s_tcw[0], s_tcw[1], cam, w, uv, RA.min_depth, RA.inlier_sq);
+        const bool in = consensus && robust_inlier(S.s_tcw[0], S.s_tcw[1], cam, w, uv, RA.min_depth, RA.inlier_sq);
         const int j = cam == 0 ? RA.B.pos[k] : n0 + RA.B.pos[k];
         s_mask[j] = in ? 1 : 2;
         nin += in ? 1 : 0;
@@ -698,7 +614,7 @@ __device__ __forceinline__ void pnp_robust_refit_body(const RobustArgs& RA) {
     __syncthreads();
     for (int j = tid; j < nf; j += kPnpThreads) RA.B.mask[j] = s_mask[j];
     if (tid == 0) {
-        pnp_finish(A, s_ctl, t_entry);  // -> RA.out->motion
+        pnp_finish(A, S.s_ctl, t_entry);  // -> RA.out->motion
         rsvio_robust_motion_result* o = RA.out;
         const int n_pairs = RA.B.counts[1];
         o->ransac_status = !consensus ? RSVIO_RANSAC_NO_CONSENSUS
