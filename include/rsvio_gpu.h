@@ -474,6 +474,58 @@ int rsvio_ba_batch_create(rsvio_ba* const* windows, int32_t n, rsvio_ba_batch** 
 int rsvio_ba_batch_run(rsvio_ba_batch* batch, const rsvio_lm_cfg* cfg, rsvio_ba_result* results);
 void rsvio_ba_batch_destroy(rsvio_ba_batch* batch);
 
+/* The batched keyframe step: what a window calls around its solve -- rsvio_ba_triangulate,
+ * rsvio_ba_check_landmarks, rsvio_ba_covariance -- for all windows of a batch by one launch (chain)
+ * each, and the solve of a subset.  `active` is n bytes, one per window of the batch (NULL: every
+ * window).  A window that is not active is not read, written or required to hold a problem, and its
+ * slot / result is left untouched.  Slot i is window i's; per slot the semantics are exactly the
+ * single call's (the same kernels' code on the window as a grid dimension: the same bits).
+ * Everything is checked before anything is launched or written: RSVIO_ERR_INVALID_ARG, with
+ * rsvio_last_error naming the slot, for an active window without a problem, with a solve in flight
+ * (rsvio_ba_run_async not waited), an n_lm that differs from the problem's, a bad landmark
+ * selection, or huber_delta <= 0 / NaN.  The calls run on the batch's stream after, on the device,
+ * what each active window's own stream has enqueued; where a call returns without a host wait
+ * (the enqueue-only triangulate) each active window's stream is made to wait for the batch's kernel
+ * by an event, so a later single-handle call on the window sees the batch's writes.  *device_ms
+ * (may be NULL): the call's kernels by HIP events; 0 when the call only enqueued. */
+/* rsvio_ba_batch_run over the active windows only (rsvio_ba_batch_run is the NULL case). */
+int rsvio_ba_batch_run_active(rsvio_ba_batch* batch, const uint8_t* active, const rsvio_lm_cfg* cfg,
+                              rsvio_ba_result* results);
+typedef struct {
+    const uint8_t* lm_mask;           /* triangulate: n_lm bytes, NULL = all landmarks; check: ignored */
+    const rsvio_landmark_gate* gate;  /* NULL: the call's gate */
+    double* p_W_out;                  /* triangulate: n_lm x 3, the initial points as the next run sees them; or NULL */
+    rsvio_landmark_info* info_out;    /* n_lm, or NULL */
+    int32_t n_lm;                     /* must be the window's landmark count */
+    int32_t n_ok;                     /* out: landmarks reported OK; -1 when the call only enqueued */
+    int32_t status;                   /* out: RSVIO_OK */
+    int32_t reserved;
+} rsvio_ba_landmark_slot;             /* 48 bytes */
+/* rsvio_ba_triangulate per active window.  `gate` may be NULL only if every active slot has its own.
+ * With p_W_out and info_out NULL in every active slot the call only enqueues (set_problem x n ->
+ * batch_triangulate -> batch_run_active has no host wait); otherwise one host wait for the call. */
+int rsvio_ba_batch_triangulate(rsvio_ba_batch* batch, const uint8_t* active, const rsvio_landmark_gate* gate,
+                               rsvio_ba_landmark_slot* slots, double* device_ms);
+/* rsvio_ba_check_landmarks per active window (reads only; one host wait). */
+int rsvio_ba_batch_check_landmarks(rsvio_ba_batch* batch, const uint8_t* active, const rsvio_landmark_gate* gate,
+                                   rsvio_ba_landmark_slot* slots, double* device_ms);
+typedef struct {
+    double* cov_cc;                   /* as rsvio_ba_covariance's arguments of the same names */
+    double* cov_pose;
+    const int32_t* lm_idx;
+    double* cov_lm;
+    uint8_t* lm_flags;
+    int32_t n_sel;
+    int32_t reserved;
+    rsvio_cov_info info;              /* out; device_ms is the whole call's */
+} rsvio_ba_cov_slot;                  /* 80 bytes */
+/* rsvio_ba_covariance per active window by one launch chain (K4, K4c, the camera covariance once
+ * per distinct solver template among the windows, the landmark covariance) and at most two host
+ * waits whatever n is.  A singular window is a normal slot result (info.status < 0, nothing else
+ * written for it).  The state, and what any later run computes, is untouched. */
+int rsvio_ba_batch_covariance(rsvio_ba_batch* batch, const uint8_t* active, double huber_delta,
+                              rsvio_ba_cov_slot* slots, double* device_ms);
+
 /* Landmark sharding over ranks: each rank uploads only its own
  * landmarks/observations; the reduced system and costs are summed with RCCL over xGMI. */
 int rsvio_rccl_unique_id(uint8_t* out, size_t cap);   /* cap >= 128 */

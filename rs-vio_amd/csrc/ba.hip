@@ -4716,25 +4716,34 @@ struct BundleAdjuster {
         }
     }
 
-    // Pose and landmark covariance at the state get_state would return (ba_covariance.hpp).  The
-    // chain relinearises that state into raw buffer 0 -- scratch between solves: every start
-    // linearises the initial state into it again -- by K4 itself, handed x as its initial state and
-    // scratch as the state buffers, LM state and stamp its folded-in reset writes; K4c then runs
-    // on an LM state of the call's own {lambda 0, nothing pending}.  So neither the state buffers
-    // nor the handle's LM states are written.  The outputs are copied out only on a positive status.
-    void covariance(double huber_delta, double* cov_cc, double* cov_pose, const int32_t* lm_idx, int32_t n_sel,
-                    double* cov_lm, uint8_t* lm_flags, rsvio_cov_info* info) {
-        if (pend.active) throw CallOrderError("covariance: a solve is in flight (call rsvio_ba_wait first)");
-        if (sharded()) throw CallOrderError("covariance: not available on a landmark-sharded handle");
-        if (!has_problem) throw std::invalid_argument("covariance: no problem uploaded");
-        if (!(huber_delta > 0.0)) throw std::invalid_argument("covariance: huber_delta must be positive");
-        const int n_lm = G.n_lm, n_kf = G.n_kf, n = 6 * G.n_free;
+    // the argument checks of covariance, single and batched (what: the caller's prefix)
+    void cov_check(const std::string& what, double huber_delta, const int32_t* lm_idx, int32_t n_sel,
+                   const double* cov_lm, const uint8_t* lm_flags) const {
+        if (pend.active) throw CallOrderError(what + ": a solve is in flight (call rsvio_ba_wait first)");
+        if (sharded()) throw CallOrderError(what + ": not available on a landmark-sharded handle");
+        if (!has_problem) throw std::invalid_argument(what + ": no problem uploaded");
+        if (!(huber_delta > 0.0)) throw std::invalid_argument(what + ": huber_delta must be positive");
+        const int n_lm = G.n_lm;
         if (n_sel < 0 || (n_sel > 0 && (!cov_lm || !lm_flags)) || (!lm_idx && n_sel != 0 && n_sel != n_lm))
-            throw std::invalid_argument("covariance: landmark selection and its outputs do not match");
+            throw std::invalid_argument(what + ": landmark selection and its outputs do not match");
         if (lm_idx)
             for (int i = 0; i < n_sel; ++i)
-                if (lm_idx[i] < 0 || lm_idx[i] >= n_lm) throw std::invalid_argument("covariance: lm_idx out of range");
-        settle();
+                if (lm_idx[i] < 0 || lm_idx[i] >= n_lm) throw std::invalid_argument(what + ": lm_idx out of range");
+    }
+
+    // What the covariance chain of this window runs on: K4's and K4c's Work views, the geometry at
+    // the call's Huber delta, the outputs in the handle's scratch and the staged selection.
+    struct CovPlan {
+        Geometry Gc;
+        Prob pr;
+        Work wl, wk;
+        CovOut O;
+        const unsigned char* d_sel;
+    };
+    // Grows the handle's scratch, stages the selection and builds the views (arguments checked by
+    // cov_check; nothing is enqueued).
+    CovPlan cov_plan(double huber_delta, const int32_t* lm_idx, int32_t n_sel) {
+        const int n_lm = G.n_lm, n_kf = G.n_kf, n = 6 * G.n_free;
         if (!ev_cov0) {
             RSVIO_HIP(hipEventCreate(&ev_cov0));
             RSVIO_HIP(hipEventCreate(&ev_cov1));
@@ -4750,13 +4759,14 @@ struct BundleAdjuster {
         const size_t n_out = n_res + (size_t)7 * n_kf + (size_t)3 * std::max(n_lm, 1) + 2;
         grow(d_cov, n_out);
         grow(d_cov_flags, (size_t)std::max(n_lm, 1));
-        const unsigned char* d_sel = nullptr;
+        CovPlan c;
+        c.d_sel = nullptr;
         if (n_lm && (lm_idx || n_sel == 0)) {
             if (sel_pending) RSVIO_HIP(hipEventSynchronize(ev_sel));
             sel_pending = false;
             std::memset(h_lm_sel.p, 0, (size_t)n_lm);
             for (int i = 0; i < n_sel; ++i) h_lm_sel.p[lm_idx[i]] = 1;
-            d_sel = h_lm_sel_dev;
+            c.d_sel = h_lm_sel_dev;
         }
         Work wk = work_at(0);
         const double *pose = wk.pose_init, *pw = wk.pw_init;
@@ -4781,16 +4791,80 @@ struct BundleAdjuster {
         wk.rawl[1] = wk.rawl[0];
         wk.st_prev = d_cov_state.p;
         wk.st = d_cov_state.p + 1;
-        Geometry Gc = G;
-        Gc.huber_delta = huber_delta;
-        Gc.chol = 0;
-        const Prob pr = prob();
-        CovOut O;
-        O.cc = d_cov.p;
-        O.lm = d_cov.p + (size_t)n * n;
-        O.cost = O.lm + (size_t)9 * std::max(n_lm, 1);
-        O.flags = d_cov_flags.p;
-        O.cst = d_cov_st.p;
+        c.Gc = G;
+        c.Gc.huber_delta = huber_delta;
+        c.Gc.chol = 0;
+        c.pr = prob();
+        c.wl = wl;
+        c.wk = wk;
+        c.O.cc = d_cov.p;
+        c.O.lm = d_cov.p + (size_t)n * n;
+        c.O.cost = c.O.lm + (size_t)9 * std::max(n_lm, 1);
+        c.O.flags = d_cov_flags.p;
+        c.O.cst = d_cov_st.p;
+        return c;
+    }
+    const unsigned long long* obs_mask_dev() const {
+        return reinterpret_cast<const unsigned long long*>(d_arena.p + lay.mask);
+    }
+    static void cov_fill_info(rsvio_cov_info* info, int n_free, const int cst[2], double cost, float ms) {
+        info->n_free = n_free;
+        info->n_singular = cst[1];
+        info->reserved = 0;
+        info->cost = cost;
+        info->device_ms = ms;
+        info->status = cst[1] > 0 ? RSVIO_COV_LANDMARK_SINGULAR : cst[0] == 1 ? RSVIO_COV_OK : RSVIO_COV_CAMERA_SINGULAR;
+    }
+    // the outputs of an OK chain: their copies enqueued on s into the handle's host buffers ...
+    void cov_fetch(const CovOut& O, bool want_cc, int32_t n_sel, hipStream_t s) {
+        const int n_lm = G.n_lm, n = 6 * G.n_free;
+        if (want_cc) {
+            cov_host.resize((size_t)n * n);
+            RSVIO_HIP(hipMemcpyAsync(cov_host.data(), O.cc, sizeof(double) * cov_host.size(), hipMemcpyDeviceToHost, s));
+        }
+        if (n_sel > 0) {
+            cov_lm_host.resize((size_t)9 * n_lm);
+            cov_flags_host.resize((size_t)n_lm);
+            RSVIO_HIP(hipMemcpyAsync(cov_lm_host.data(), O.lm, sizeof(double) * cov_lm_host.size(),
+                                     hipMemcpyDeviceToHost, s));
+            RSVIO_HIP(hipMemcpyAsync(cov_flags_host.data(), O.flags, (size_t)n_lm, hipMemcpyDeviceToHost, s));
+        }
+    }
+    // ... and, once s is synchronised, handed to the caller
+    void cov_deliver(double* cov_cc, double* cov_pose, const int32_t* lm_idx, int32_t n_sel, double* cov_lm,
+                     uint8_t* lm_flags) const {
+        const int n_kf = G.n_kf, n = 6 * G.n_free;
+        if (cov_cc) std::memcpy(cov_cc, cov_host.data(), sizeof(double) * cov_host.size());
+        if (cov_pose)
+            for (int k = 0; k < n_kf; ++k) {
+                const int f = hs_free[k];
+                for (int i = 0; i < 6; ++i)
+                    for (int j = 0; j < 6; ++j)
+                        cov_pose[36 * k + 6 * i + j] = f < 0 ? 0.0 : cov_host[(size_t)(6 * f + i) * n + 6 * f + j];
+            }
+        for (int i = 0; i < n_sel; ++i) {
+            const int l = lm_idx ? lm_idx[i] : i;
+            std::memcpy(cov_lm + (size_t)9 * i, cov_lm_host.data() + (size_t)9 * l, 9 * sizeof(double));
+            lm_flags[i] = cov_flags_host[l];
+        }
+    }
+
+    // Pose and landmark covariance at the state get_state would return (ba_covariance.hpp).  The
+    // chain relinearises that state into raw buffer 0 -- scratch between solves: every start
+    // linearises the initial state into it again -- by K4 itself, handed x as its initial state and
+    // scratch as the state buffers, LM state and stamp its folded-in reset writes; K4c then runs
+    // on an LM state of the call's own {lambda 0, nothing pending}.  So neither the state buffers
+    // nor the handle's LM states are written.  The outputs are copied out only on a positive status.
+    void covariance(double huber_delta, double* cov_cc, double* cov_pose, const int32_t* lm_idx, int32_t n_sel,
+                    double* cov_lm, uint8_t* lm_flags, rsvio_cov_info* info) {
+        cov_check("covariance", huber_delta, lm_idx, n_sel, cov_lm, lm_flags);
+        const int n_lm = G.n_lm;
+        settle();
+        const CovPlan c = cov_plan(huber_delta, lm_idx, n_sel);
+        const Geometry& Gc = c.Gc;
+        const Prob& pr = c.pr;
+        const Work &wl = c.wl, &wk = c.wk;
+        const CovOut& O = c.O;
         settled = false;
         RSVIO_HIP(hipMemsetAsync(d_cov_st.p, 0, 2 * sizeof(int), stream));
         RSVIO_HIP(hipEventRecord(ev_cov0, stream));
@@ -4809,7 +4883,7 @@ struct BundleAdjuster {
                 dispatch_block_nf(bk_template_nf(G.n_free), launch);
         }
         hipLaunchKernelGGL(ba_landmark_covariance, dim3(std::max(G.n_wave + (n_lm + 63) / 64, 1)), dim3(64), 0, stream,
-                           Gc, pr, wk, reinterpret_cast<const unsigned long long*>(d_arena.p + lay.mask), d_sel, O);
+                           Gc, pr, wk, obs_mask_dev(), c.d_sel, O);
         RSVIO_HIP(hipGetLastError());
         RSVIO_HIP(hipEventRecord(ev_cov1, stream));
         RSVIO_HIP(hipMemsetAsync(d_singular.p, 0, sizeof(int), stream));  // K4c may have set it
@@ -4820,39 +4894,11 @@ struct BundleAdjuster {
         RSVIO_HIP(hipStreamSynchronize(stream));
         float ms = 0.0f;
         RSVIO_HIP(hipEventElapsedTime(&ms, ev_cov0, ev_cov1));
-        info->n_free = G.n_free;
-        info->n_singular = cst[1];
-        info->reserved = 0;
-        info->cost = cost;
-        info->device_ms = ms;
-        info->status = cst[1] > 0 ? RSVIO_COV_LANDMARK_SINGULAR : cst[0] == 1 ? RSVIO_COV_OK : RSVIO_COV_CAMERA_SINGULAR;
+        cov_fill_info(info, G.n_free, cst, cost, ms);
         if (info->status == RSVIO_COV_OK) {
-            if (cov_cc || cov_pose) {
-                cov_host.resize((size_t)n * n);
-                RSVIO_HIP(hipMemcpyAsync(cov_host.data(), O.cc, sizeof(double) * cov_host.size(), hipMemcpyDeviceToHost,
-                                         stream));
-            }
-            if (n_sel > 0) {
-                cov_lm_host.resize((size_t)9 * n_lm);
-                cov_flags_host.resize((size_t)n_lm);
-                RSVIO_HIP(hipMemcpyAsync(cov_lm_host.data(), O.lm, sizeof(double) * cov_lm_host.size(),
-                                         hipMemcpyDeviceToHost, stream));
-                RSVIO_HIP(hipMemcpyAsync(cov_flags_host.data(), O.flags, (size_t)n_lm, hipMemcpyDeviceToHost, stream));
-            }
+            cov_fetch(O, cov_cc || cov_pose, n_sel, stream);
             RSVIO_HIP(hipStreamSynchronize(stream));
-            if (cov_cc) std::memcpy(cov_cc, cov_host.data(), sizeof(double) * cov_host.size());
-            if (cov_pose)
-                for (int k = 0; k < n_kf; ++k) {
-                    const int f = hs_free[k];
-                    for (int i = 0; i < 6; ++i)
-                        for (int j = 0; j < 6; ++j)
-                            cov_pose[36 * k + 6 * i + j] = f < 0 ? 0.0 : cov_host[(size_t)(6 * f + i) * n + 6 * f + j];
-                }
-            for (int i = 0; i < n_sel; ++i) {
-                const int l = lm_idx ? lm_idx[i] : i;
-                std::memcpy(cov_lm + (size_t)9 * i, cov_lm_host.data() + (size_t)9 * l, 9 * sizeof(double));
-                lm_flags[i] = cov_flags_host[l];
-            }
+            cov_deliver(cov_cc, cov_pose, lm_idx, n_sel, cov_lm, lm_flags);
         }
         settled = true;
     }
@@ -4915,6 +4961,20 @@ struct BundleBatch {
     HostBuf<int> h_dmap;
     std::vector<hipEvent_t> ev_win;  // per window: its stream's pending work (an upload) before the batch
     int last_iterations = 3;
+    // the batched keyframe step (triangulate, check, covariance): the landmark kernels' table has
+    // its own pinned image and an event for its upload, because an enqueue-only triangulate
+    // returns before the copy has read it; the covariance's status words and costs sit in one
+    // array of the batch (one read-back for all windows), its other scratch is each handle's
+    DevBuf<LmDesc> d_lmdesc;
+    HostBuf<LmDesc> h_lmdesc;
+    hipEvent_t ev_lmcopy = nullptr, ev_after = nullptr;
+    bool lmcopy_pending = false;
+    DevBuf<CovDesc> d_covdesc;
+    HostBuf<CovDesc> h_covdesc;
+    DevBuf<int> d_cst;
+    HostBuf<int> h_cst;
+    DevBuf<double> d_cost;
+    HostBuf<double> h_cost;
 
     void init(BundleAdjuster* const* w, int n) {
         if (n < 1) throw std::invalid_argument("a batch needs at least one window");
@@ -4936,9 +4996,21 @@ struct BundleBatch {
         d_desc.alloc(n);
         h_desc.alloc(n);
         h_states.alloc(n, hipHostMallocCoherent);
+        RSVIO_HIP(hipEventCreateWithFlags(&ev_lmcopy, hipEventDisableTiming));
+        RSVIO_HIP(hipEventCreateWithFlags(&ev_after, hipEventDisableTiming));
+        d_lmdesc.alloc(n);
+        h_lmdesc.alloc(n);
+        d_covdesc.alloc(n);
+        h_covdesc.alloc(n);
+        d_cst.alloc(2 * (size_t)n);
+        h_cst.alloc(2 * (size_t)n);
+        d_cost.alloc(n);
+        h_cost.alloc(n);
     }
     ~BundleBatch() {
         if (stream) (void)hipStreamSynchronize(stream);
+        if (ev_lmcopy) (void)hipEventDestroy(ev_lmcopy);
+        if (ev_after) (void)hipEventDestroy(ev_after);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         for (hipEvent_t e : ev_win)
@@ -4959,16 +5031,28 @@ struct BundleBatch {
         RSVIO_HIP(hipGetLastError());
     }
 
-    void run(const rsvio_lm_cfg& cfg, rsvio_ba_result* res) {
+    // on: one byte per window (null = every window).  A window that is off is a skipped row of the
+    // descriptor table: it is not read, written or required to hold a problem, and res[i] is left.
+    void run(const rsvio_lm_cfg& cfg, rsvio_ba_result* res, const uint8_t* on = nullptr) {
         const int B = (int)win.size();
         int nf = 1, max_wave = 1, max_chunk = 1, active = 0;
         std::vector<int> skip(B, 0);
         size_t ne_total = 0;
         for (int i = 0; i < B; ++i) {
+            if (on && !on[i]) continue;
+            const BundleAdjuster& w = *win[i];
+            const std::string slot = on ? " (window " + std::to_string(i) + ")" : std::string();
+            if (w.pend.active)
+                throw CallOrderError("rsvio_ba_batch_run: a solve is in flight (call rsvio_ba_wait first)" + slot);
+            if (!w.has_problem) throw std::invalid_argument("batch window without a problem" + slot);
+        }
+        for (int i = 0; i < B; ++i) {
+            if (on && !on[i]) {
+                skip[i] = 2;
+                continue;
+            }
             BundleAdjuster& w = *win[i];
-            if (w.pend.active) throw CallOrderError("rsvio_ba_batch_run: a solve is in flight (call rsvio_ba_wait first)");
             w.state_export = false;  // the batch's decisions leave the state in device memory
-            if (!w.has_problem) throw std::invalid_argument("batch window without a problem");
             const Geometry& G = w.G;
             // sliding_window.rs:303-319 guards, as the single-window start()
             skip[i] = (G.n_obs < 6 || G.n_obs < G.n_kf + G.n_lm || G.n_wave == 0) ? 1 : 0;
@@ -4991,6 +5075,11 @@ struct BundleBatch {
         for (int i = 0; i < B; ++i) {
             BundleAdjuster& w = *win[i];
             WinDesc& d = h_desc.p[i];
+            if (skip[i] == 2) {  // off: no field of the handle is read
+                d = WinDesc{};
+                d.skip = 1;
+                continue;
+            }
             d.skip = skip[i];
             d.G = w.G;
             d.G.huber_delta = cfg.huber_delta;
@@ -5008,7 +5097,7 @@ struct BundleBatch {
             off += ne;
         }
         for (int i = 0; i < B; ++i) {
-            if (skip[i]) {
+            if (skip[i] == 1) {
                 res[i] = rsvio_ba_result{};
                 res[i].status = RSVIO_LM_SKIPPED;
             }
@@ -5019,7 +5108,7 @@ struct BundleBatch {
         // window's stream instead of synchronising the host
         for (int i = 0; i < B; ++i) {
             BundleAdjuster& w = *win[i];
-            if (w.settled) continue;
+            if (skip[i] == 2 || w.settled) continue;
             RSVIO_HIP(hipEventRecord(ev_win[i], w.stream));
             RSVIO_HIP(hipStreamWaitEvent(stream, ev_win[i], 0));
         }
@@ -5075,6 +5164,241 @@ struct BundleBatch {
             res[i].initial_cost = st.initial_cost;
             res[i].final_cost = st.cost;
             res[i].solve_ms = ms;
+        }
+    }
+
+    // the batch stream waits, on the device, for what window i's own stream still has enqueued
+    void after_window(int i) {
+        BundleAdjuster& w = *win[i];
+        if (w.settled) return;
+        RSVIO_HIP(hipEventRecord(ev_win[i], w.stream));
+        RSVIO_HIP(hipStreamWaitEvent(stream, ev_win[i], 0));
+    }
+    // after a host wait on the batch stream: window i's stream ran nothing since after_window
+    void idle_window(int i) {
+        BundleAdjuster& w = *win[i];
+        w.settled = true;
+        w.sel_pending = false;
+        w.destroy_retired();
+    }
+
+    // rsvio_ba_batch_triangulate (tri) / _check_landmarks: BundleAdjuster::landmarks per slot, by
+    // one bab_landmarks launch.  The gates were validated by the caller (gate[i]: slot i's).
+    void landmarks(bool tri, const uint8_t* on, const std::vector<const rsvio_landmark_gate*>& gate,
+                   rsvio_ba_landmark_slot* slots, double* device_ms) {
+        const std::string what = tri ? "rsvio_ba_batch_triangulate" : "rsvio_ba_batch_check_landmarks";
+        const int B = (int)win.size();
+        int n_act = 0;
+        bool want = !tri;
+        for (int i = 0; i < B; ++i) {
+            if (on && !on[i]) continue;
+            const BundleAdjuster& w = *win[i];
+            const std::string slot = " (slot " + std::to_string(i) + ")";
+            if (w.pend.active) throw CallOrderError(what + ": a solve is in flight (call rsvio_ba_wait first)" + slot);
+            if (!w.has_problem) throw std::invalid_argument(what + ": no problem uploaded" + slot);
+            if (slots[i].n_lm != w.G.n_lm)
+                throw std::invalid_argument(what + ": n_lm differs from the uploaded problem's" + slot);
+            ++n_act;
+            want = want || (tri && slots[i].p_W_out) || slots[i].info_out;
+        }
+        if (device_ms) *device_ms = 0.0;
+        if (!n_act) return;
+        if (lmcopy_pending) RSVIO_HIP(hipEventSynchronize(ev_lmcopy));  // the last upload has read the image
+        lmcopy_pending = false;
+        int max_blocks = 0;
+        std::vector<char> live(B, 0);
+        for (int i = 0; i < B; ++i) {
+            LmDesc& d = h_lmdesc.p[i];
+            d = LmDesc{};
+            d.skip = 1;
+            if (on && !on[i]) continue;
+            BundleAdjuster& w = *win[i];
+            rsvio_ba_landmark_slot& sl = slots[i];
+            sl.n_ok = want ? 0 : -1;
+            sl.status = RSVIO_OK;
+            const int n_lm = w.G.n_lm;
+            if (!n_lm) continue;
+            live[i] = 1;
+            if (tri && sl.lm_mask) {
+                if (w.sel_pending) RSVIO_HIP(hipEventSynchronize(w.ev_sel));  // its last reader is done
+                w.sel_pending = false;
+                std::memcpy(w.h_lm_sel.p, sl.lm_mask, (size_t)n_lm);
+                d.sel = w.h_lm_sel_dev;
+            }
+            const Work wk = w.work_at(0);
+            d.pose = wk.pose_init;
+            d.pw = wk.pw_init;
+            if (tri) {
+                if (w.at_initial) w.state_fresh = true;
+            } else if (!w.state_fresh) {
+                const int cur = w.h_state.p->cur;
+                d.pose = wk.pose[cur];
+                d.pw = wk.pw[cur];
+            }
+            const rsvio_landmark_gate& g = *gate[i];
+            d.gate = LmGate{tri ? g.mode : (int)RSVIO_TRI_ALL_VIEWS, g.min_depth, g.max_depth, g.max_sq_error};
+            d.G = w.G;
+            d.Pr = w.prob();
+            d.obs_mask = w.obs_mask_dev();
+            d.pw_out = reinterpret_cast<double*>(w.d_arena.p + w.lay.pw_init);
+            d.info = w.d_lm_info.p;
+            d.skip = 0;
+            max_blocks = std::max(max_blocks, w.G.n_wave + (n_lm + 63) / 64);
+        }
+        if (!max_blocks) return;
+        for (int i = 0; i < B; ++i)
+            if (live[i]) after_window(i);
+        RSVIO_HIP(hipMemcpyAsync(d_lmdesc.p, h_lmdesc.p, sizeof(LmDesc) * B, hipMemcpyHostToDevice, stream));
+        RSVIO_HIP(hipEventRecord(ev_lmcopy, stream));
+        lmcopy_pending = true;
+        RSVIO_HIP(hipEventRecord(ev0, stream));
+        if (tri)
+            hipLaunchKernelGGL(bab_landmarks<true>, dim3(max_blocks, B), dim3(64), 0, stream, d_lmdesc.p);
+        else
+            hipLaunchKernelGGL(bab_landmarks<false>, dim3(max_blocks, B), dim3(64), 0, stream, d_lmdesc.p);
+        RSVIO_HIP(hipGetLastError());
+        RSVIO_HIP(hipEventRecord(ev1, stream));
+        for (int i = 0; i < B; ++i) {
+            if (!live[i]) continue;
+            BundleAdjuster& w = *win[i];
+            w.settled = false;
+            if (h_lmdesc.p[i].sel) {
+                RSVIO_HIP(hipEventRecord(w.ev_sel, stream));
+                w.sel_pending = true;
+            }
+        }
+        if (!want) {
+            // enqueue only: whatever a window's own stream runs next comes after the batch's kernel
+            RSVIO_HIP(hipEventRecord(ev_after, stream));
+            for (int i = 0; i < B; ++i)
+                if (live[i]) RSVIO_HIP(hipStreamWaitEvent(win[i]->stream, ev_after, 0));
+            return;
+        }
+        for (int i = 0; i < B; ++i) {
+            if (!live[i]) continue;
+            BundleAdjuster& w = *win[i];
+            const size_t n_lm = (size_t)w.G.n_lm;
+            if (tri && slots[i].p_W_out)
+                RSVIO_HIP(hipMemcpyAsync(slots[i].p_W_out, h_lmdesc.p[i].pw_out, sizeof(double) * 3 * n_lm,
+                                         hipMemcpyDeviceToHost, stream));
+            RSVIO_HIP(hipMemcpyAsync(w.h_lm_info.p, w.d_lm_info.p, sizeof(rsvio_landmark_info) * n_lm,
+                                     hipMemcpyDeviceToHost, stream));
+        }
+        RSVIO_HIP(hipStreamSynchronize(stream));
+        lmcopy_pending = false;
+        float ms = 0.0f;
+        RSVIO_HIP(hipEventElapsedTime(&ms, ev0, ev1));
+        if (device_ms) *device_ms = ms;
+        for (int i = 0; i < B; ++i) {
+            if (!live[i]) continue;
+            BundleAdjuster& w = *win[i];
+            idle_window(i);
+            const int n_lm = w.G.n_lm;
+            if (slots[i].info_out)
+                std::memcpy(slots[i].info_out, w.h_lm_info.p, sizeof(rsvio_landmark_info) * (size_t)n_lm);
+            int32_t c = 0;
+            for (int l = 0; l < n_lm; ++l) c += (w.h_lm_info.p[l].flags & RSVIO_LM_OK) ? 1 : 0;
+            slots[i].n_ok = c;
+        }
+    }
+
+    // rsvio_ba_batch_covariance: BundleAdjuster::covariance per slot by one launch chain -- K4 and
+    // K4c on a table of each window's covariance views, the camera covariance once per distinct
+    // template among the windows, the landmark covariance -- and two host waits: the statuses and
+    // costs, then the outputs of the windows that report OK.
+    void covariance(const uint8_t* on, double huber_delta, rsvio_ba_cov_slot* slots, double* device_ms) {
+        const std::string what = "rsvio_ba_batch_covariance";
+        const int B = (int)win.size();
+        if (!(huber_delta > 0.0)) throw std::invalid_argument(what + ": huber_delta must be positive");
+        int n_act = 0;
+        for (int i = 0; i < B; ++i) {
+            if (on && !on[i]) continue;
+            const BundleAdjuster& w = *win[i];
+            const std::string slot = what + " (slot " + std::to_string(i) + ")";
+            if (w.sharded()) throw std::invalid_argument(slot + ": not available on a landmark-sharded handle");
+            w.cov_check(slot, huber_delta, slots[i].lm_idx, slots[i].n_sel, slots[i].cov_lm, slots[i].lm_flags);
+            ++n_act;
+        }
+        if (device_ms) *device_ms = 0.0;
+        if (!n_act) return;
+        int max_wave = 1, max_chunk = 1, max_blocks = 1;
+        std::vector<int> tmpl;  // the distinct camera templates, in order of first appearance
+        for (int i = 0; i < B; ++i) {
+            WinDesc& d = h_desc.p[i];
+            CovDesc& c = h_covdesc.p[i];
+            d = WinDesc{};
+            c = CovDesc{};
+            d.skip = 1;
+            if (on && !on[i]) continue;
+            BundleAdjuster& w = *win[i];
+            const BundleAdjuster::CovPlan p = w.cov_plan(huber_delta, slots[i].lm_idx, slots[i].n_sel);
+            d.skip = 0;
+            d.G = p.Gc;
+            d.Pr = p.pr;
+            d.W[0] = d.W[1] = p.wk;
+            d.W[2] = d.W[3] = p.wl;
+            c.O = p.O;
+            c.O.cst = d_cst.p + 2 * i;
+            c.O.cost = d_cost.p + i;
+            c.obs_mask = w.obs_mask_dev();
+            c.sel = p.d_sel;
+            const int nf = w.G.n_free;
+            c.nf = nf <= 10 ? nf : bk_template_nf(nf);
+            if (c.nf > 0 && std::find(tmpl.begin(), tmpl.end(), c.nf) == tmpl.end()) tmpl.push_back(c.nf);
+            max_wave = std::max(max_wave, w.G.n_wave);
+            max_chunk = std::max(max_chunk, w.G.n_chunk);
+            max_blocks = std::max(max_blocks, w.G.n_wave + (w.G.n_lm + 63) / 64);
+        }
+        max_wave = (max_wave + kGrp - 1) / kGrp * kGrp;  // wave w on XCD w % 8 in every window, as run()
+        for (int i = 0; i < B; ++i)
+            if (!h_desc.p[i].skip) after_window(i);
+        RSVIO_HIP(hipMemcpyAsync(d_desc.p, h_desc.p, sizeof(WinDesc) * B, hipMemcpyHostToDevice, stream));
+        RSVIO_HIP(hipMemcpyAsync(d_covdesc.p, h_covdesc.p, sizeof(CovDesc) * B, hipMemcpyHostToDevice, stream));
+        RSVIO_HIP(hipMemsetAsync(d_cst.p, 0, sizeof(int) * 2 * B, stream));
+        RSVIO_HIP(hipEventRecord(ev0, stream));
+        hipLaunchKernelGGL(bab_linearize, dim3(max_wave, B), dim3(64), 0, stream, d_desc.p, 0.0);
+        hipLaunchKernelGGL(bab_schur_chunks, dim3(max_chunk, B), dim3(kSchurThreads), 0, stream, d_desc.p, 0,
+                           LmArgs{1, 0.0, 0.0});
+        for (int nf : tmpl) {
+            auto launch = [&](auto c) {
+                constexpr int NF = decltype(c)::value;
+                hipLaunchKernelGGL(bab_camera_covariance<NF>, dim3(B), dim3(NF <= 10 ? kK5Threads : 64 * kBkWaves), 0,
+                                   stream, d_desc.p, d_covdesc.p);
+            };
+            if (!(dispatch_panel_nf(nf, launch) || dispatch_block_nf(nf, launch)))
+                throw std::logic_error("batched covariance: no camera template for this window size");
+        }
+        hipLaunchKernelGGL(bab_landmark_covariance, dim3(max_blocks, B), dim3(64), 0, stream, d_desc.p, d_covdesc.p);
+        RSVIO_HIP(hipGetLastError());
+        RSVIO_HIP(hipEventRecord(ev1, stream));
+        for (int i = 0; i < B; ++i) {
+            if (h_desc.p[i].skip) continue;
+            win[i]->settled = false;
+            RSVIO_HIP(hipMemsetAsync(win[i]->d_singular.p, 0, sizeof(int), stream));  // K4c may have set it
+        }
+        RSVIO_HIP(hipMemcpyAsync(h_cst.p, d_cst.p, sizeof(int) * 2 * B, hipMemcpyDeviceToHost, stream));
+        RSVIO_HIP(hipMemcpyAsync(h_cost.p, d_cost.p, sizeof(double) * B, hipMemcpyDeviceToHost, stream));
+        RSVIO_HIP(hipStreamSynchronize(stream));
+        float ms = 0.0f;
+        RSVIO_HIP(hipEventElapsedTime(&ms, ev0, ev1));
+        if (device_ms) *device_ms = ms;
+        bool any_ok = false;
+        for (int i = 0; i < B; ++i) {
+            if (h_desc.p[i].skip) continue;
+            BundleAdjuster& w = *win[i];
+            rsvio_ba_cov_slot& sl = slots[i];
+            BundleAdjuster::cov_fill_info(&sl.info, w.G.n_free, h_cst.p + 2 * i, h_cost.p[i], ms);
+            if (sl.info.status != RSVIO_COV_OK) continue;
+            w.cov_fetch(h_covdesc.p[i].O, sl.cov_cc || sl.cov_pose, sl.n_sel, stream);
+            any_ok = true;
+        }
+        if (any_ok) RSVIO_HIP(hipStreamSynchronize(stream));
+        for (int i = 0; i < B; ++i) {
+            if (h_desc.p[i].skip) continue;
+            const rsvio_ba_cov_slot& sl = slots[i];
+            if (sl.info.status == RSVIO_COV_OK)
+                win[i]->cov_deliver(sl.cov_cc, sl.cov_pose, sl.lm_idx, sl.n_sel, sl.cov_lm, sl.lm_flags);
+            idle_window(i);
         }
     }
 };
@@ -5276,6 +5600,60 @@ int rsvio_ba_batch_run(rsvio_ba_batch* batch, const rsvio_lm_cfg* cfg, rsvio_ba_
     if (!batch || !cfg || !results) return RSVIO_ERR_INVALID_ARG;
     return guarded([&] {
         batch->b.run(*cfg, results);
+        return (int)RSVIO_OK;
+    });
+}
+
+int rsvio_ba_batch_run_active(rsvio_ba_batch* batch, const uint8_t* active, const rsvio_lm_cfg* cfg,
+                              rsvio_ba_result* results) {
+    if (!batch || !cfg || !results) {
+        rsvio::set_last_error("rsvio_ba_batch_run_active: null batch, cfg or results");
+        return RSVIO_ERR_INVALID_ARG;
+    }
+    return guarded([&] {
+        batch->b.run(*cfg, results, active);
+        return (int)RSVIO_OK;
+    });
+}
+
+static int batch_landmarks(bool tri, rsvio_ba_batch* batch, const uint8_t* active, const rsvio_landmark_gate* gate,
+                           rsvio_ba_landmark_slot* slots, double* device_ms) {
+    const std::string what = tri ? "rsvio_ba_batch_triangulate" : "rsvio_ba_batch_check_landmarks";
+    if (!batch || !slots) {
+        rsvio::set_last_error(what + ": null batch or slots");
+        return RSVIO_ERR_INVALID_ARG;
+    }
+    const int n = (int)batch->b.win.size();
+    std::vector<const rsvio_landmark_gate*> g(n, nullptr);
+    for (int i = 0; i < n; ++i) {
+        if (active && !active[i]) continue;
+        g[i] = slots[i].gate ? slots[i].gate : gate;
+        if (!gate_ok(g[i], (what + " (slot " + std::to_string(i) + ")").c_str())) return RSVIO_ERR_INVALID_ARG;
+    }
+    return guarded([&] {
+        batch->b.landmarks(tri, active, g, slots, device_ms);
+        return (int)RSVIO_OK;
+    });
+}
+
+int rsvio_ba_batch_triangulate(rsvio_ba_batch* batch, const uint8_t* active, const rsvio_landmark_gate* gate,
+                               rsvio_ba_landmark_slot* slots, double* device_ms) {
+    return batch_landmarks(true, batch, active, gate, slots, device_ms);
+}
+
+int rsvio_ba_batch_check_landmarks(rsvio_ba_batch* batch, const uint8_t* active, const rsvio_landmark_gate* gate,
+                                   rsvio_ba_landmark_slot* slots, double* device_ms) {
+    return batch_landmarks(false, batch, active, gate, slots, device_ms);
+}
+
+int rsvio_ba_batch_covariance(rsvio_ba_batch* batch, const uint8_t* active, double huber_delta,
+                              rsvio_ba_cov_slot* slots, double* device_ms) {
+    if (!batch || !slots) {
+        rsvio::set_last_error("rsvio_ba_batch_covariance: null batch or slots");
+        return RSVIO_ERR_INVALID_ARG;
+    }
+    return guarded([&] {
+        batch->b.covariance(active, huber_delta, slots, device_ms);
         return (int)RSVIO_OK;
     });
 }

@@ -238,21 +238,22 @@ __global__ __launch_bounds__(NF <= 10 ? kK5Threads : 64 * kBkWaves) void ba_came
 // values and the flag.  The rest: 64 landmarks each, those without a slot (NOT_OBSERVED, zeros).
 // sel: one byte per landmark (null = every landmark); a landmark not selected is only tested for
 // a singular V.  Block 0 also sums the cost of x (K4's wave partials, as K5's combine does).
-__global__ __launch_bounds__(64) void ba_landmark_covariance(Geometry G, Prob Pr, Work Wk,
-                                                             const unsigned long long* obs_mask,
-                                                             const unsigned char* sel, CovOut O) {
+// bx: the block's index within its window.
+__device__ __forceinline__ void landmark_covariance_body(const Geometry& G, const Prob& Pr, const Work& Wk,
+                                                         const unsigned long long* obs_mask,
+                                                         const unsigned char* sel, const CovOut& O, int bx) {
     __shared__ double shY[18][64];
     __shared__ double shT[6][64];
     __shared__ int shF[64];
     const int lane = threadIdx.x;
-    if (blockIdx.x == 0) {
+    if (bx == 0) {
         double c = 0.0;
         for (int w = lane; w < G.n_wave; w += 64) c += Wk.partA[w * kPartA];
         c = wave_sum_det(c);
         if (lane == 0) *O.cost = c;
     }
-    if ((int)blockIdx.x >= G.n_wave) {
-        const int l = 64 * ((int)blockIdx.x - G.n_wave) + lane;
+    if (bx >= G.n_wave) {
+        const int l = 64 * (bx - G.n_wave) + lane;
         if (l < G.n_lm && obs_mask[l] == 0ull) {
 #pragma unroll
             for (int i = 0; i < 9; ++i) O.lm[(size_t)9 * l + i] = 0.0;
@@ -260,7 +261,7 @@ __global__ __launch_bounds__(64) void ba_landmark_covariance(Geometry G, Prob Pr
         }
         return;
     }
-    const int s = 64 * (int)blockIdx.x + lane;
+    const int s = 64 * bx + lane;
     const int4 h0 = Pr.slot_hdr[2 * s], h1 = Pr.slot_hdr[2 * s + 1];
     const bool act = h1.y > 0;
     const int l = h0.y, first = act ? h0.z : lane, nk = act ? h0.w : 1;
@@ -355,4 +356,55 @@ __global__ __launch_bounds__(64) void ba_landmark_covariance(Geometry G, Prob Pr
     o[3] = P[1]; o[4] = P[3]; o[5] = P[4];
     o[6] = P[2]; o[7] = P[4]; o[8] = P[5];
     O.flags[l] = RSVIO_COV_LM_OK;
+}
+
+__global__ __launch_bounds__(64) void ba_landmark_covariance(Geometry G, Prob Pr, Work Wk,
+                                                             const unsigned long long* obs_mask,
+                                                             const unsigned char* sel, CovOut O) {
+    landmark_covariance_body(G, Pr, Wk, obs_mask, sel, O, (int)blockIdx.x);
+}
+
+// Batched mode (rsvio_ba_batch_covariance).  K4 and K4c are bab_linearize / bab_schur_chunks on a
+// WinDesc table of the covariance's own views (W[2]: K4's, x as the initial state and scratch as
+// the state buffers; W[0]: K4c's and the covariance kernels', x as both state buffers), G with the
+// call's Huber delta, Pr the window's own with its own dense map.  Row i of the CovDesc table
+// beside it holds window i's outputs and the template its single call runs (nf: n_free up to 10,
+// bk_template_nf(n_free) past that, 0: no camera kernel).
+struct CovDesc {
+    CovOut O;
+    const unsigned long long* obs_mask;
+    const unsigned char* sel;
+    int nf;
+};
+
+// grid B, one workgroup per window; launched once per distinct template among the active
+// windows: the blocks of windows on another template return at once
+template <int NF>
+__global__ __launch_bounds__(NF <= 10 ? kK5Threads : 64 * kBkWaves) void bab_camera_covariance(
+    const WinDesc* __restrict__ D, const CovDesc* __restrict__ Cv) {
+    const WinDesc& d = D[blockIdx.x];
+    const CovDesc& c = Cv[blockIdx.x];
+    const int skip = d.skip, nf = c.nf;
+    const Prob Pr = d.Pr;
+    const Work& Wk = d.W[0];
+    desc_touch(Pr.dmap, Wk.cpart);
+    if (skip | (nf != NF)) return;
+    if constexpr (NF <= 10)
+        camera_covariance_panel<NF>(d.G, Pr, Wk, c.O);
+    else
+        camera_covariance_blk<NF>(d.G, Pr, Wk, c.O);
+}
+
+// grid (max over the active windows of max(n_wave + ceil(n_lm / 64), 1), B)
+__global__ __launch_bounds__(64) void bab_landmark_covariance(const WinDesc* __restrict__ D,
+                                                              const CovDesc* __restrict__ Cv) {
+    const WinDesc& d = D[blockIdx.y];
+    const CovDesc& c = Cv[blockIdx.y];
+    const int skip = d.skip, bound = max(d.G.n_wave + (d.G.n_lm + 63) / 64, 1);
+    const Prob Pr = d.Pr;
+    const Work& Wk = d.W[0];
+    const unsigned long long* obs_mask = c.obs_mask;
+    desc_touch(Pr.slot_hdr, Wk.rawl[0], Wk.partA, obs_mask);
+    if (skip | ((int)blockIdx.x >= bound)) return;
+    landmark_covariance_body(d.G, Pr, Wk, obs_mask, c.sel, c.O, (int)blockIdx.x);
 }

@@ -44,17 +44,18 @@ __device__ __forceinline__ void camera_from_world(const Pose& P, const double* T
 // landmark by its first lane, issued with the header loads): no copy precedes the kernel.
 // info: one record per landmark.  blocks [0, n_wave): the slot waves; the rest: 64 landmarks each,
 // those without a slot.
+// bx: the block's index within its window (the grid's x; a batched grid's y is the window).
 template <bool TRI>
-__global__ __launch_bounds__(64) void ba_landmarks(Geometry G, Prob Pr, const unsigned long long* obs_mask,
-                                                   const double* pose, const double* pw, double* pw_out,
-                                                   const unsigned char* sel, LmGate gate,
-                                                   rsvio_landmark_info* info) {
+__device__ __forceinline__ void landmarks_body(const Geometry& G, const Prob& Pr, const unsigned long long* obs_mask,
+                                               const double* pose, const double* pw, double* pw_out,
+                                               const unsigned char* sel, const LmGate& gate,
+                                               rsvio_landmark_info* info, int bx) {
     __shared__ double shA[10][64];  // A (packed upper, 6), r (3), observations used
     __shared__ double shP[4][64];   // the landmark's point and whether it has one, at its first lane
     __shared__ double shG[3][64];   // min depth, max depth, max squared error of the slot
     const int lane = threadIdx.x;
-    if ((int)blockIdx.x >= G.n_wave) {  // landmarks without a slot
-        const int l = 64 * ((int)blockIdx.x - G.n_wave) + lane;
+    if (bx >= G.n_wave) {  // landmarks without a slot
+        const int l = 64 * (bx - G.n_wave) + lane;
         if (l < G.n_lm && obs_mask[l] == 0ull) {
             const bool on = !TRI || !sel || __hip_atomic_load(sel + l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             rsvio_landmark_info r;
@@ -65,7 +66,7 @@ __global__ __launch_bounds__(64) void ba_landmarks(Geometry G, Prob Pr, const un
         }
         return;
     }
-    const int s = 64 * (int)blockIdx.x + lane;
+    const int s = 64 * bx + lane;
     const int4 h0 = Pr.slot_hdr[2 * s], h1 = Pr.slot_hdr[2 * s + 1];
     const double2 uvq[2] = {Pr.slot_uv[2 * s], Pr.slot_uv[2 * s + 1]};
     const bool act = h1.y > 0;
@@ -211,4 +212,41 @@ __global__ __launch_bounds__(64) void ba_landmarks(Geometry G, Prob Pr, const un
         }
     }
     info[l] = out;
+}
+
+template <bool TRI>
+__global__ __launch_bounds__(64) void ba_landmarks(Geometry G, Prob Pr, const unsigned long long* obs_mask,
+                                                   const double* pose, const double* pw, double* pw_out,
+                                                   const unsigned char* sel, LmGate gate,
+                                                   rsvio_landmark_info* info) {
+    landmarks_body<TRI>(G, Pr, obs_mask, pose, pw, pw_out, sel, gate, info, (int)blockIdx.x);
+}
+
+// Batched mode (rsvio_ba_batch_triangulate / _check_landmarks): one row per window, everything
+// the single kernel takes by value.  Grid (max over the active windows of n_wave +
+// ceil(n_lm / 64), B); a block past its window's bound, or of an inactive window, returns whole
+// before the body's first barrier.  The gate is the row's: two windows of one call may differ.
+struct LmDesc {
+    Geometry G;
+    Prob Pr;
+    const unsigned long long* obs_mask;
+    const double* pose;   // the state the single call would read: the initial poses (triangulate),
+    const double* pw;     // or what get_state would return (check)
+    double* pw_out;       // the arena's initial point array
+    const unsigned char* sel;
+    LmGate gate;
+    rsvio_landmark_info* info;
+    int skip;
+};
+
+template <bool TRI>
+__global__ __launch_bounds__(64) void bab_landmarks(const LmDesc* __restrict__ D) {
+    const LmDesc& d = D[blockIdx.y];
+    const int skip = d.skip, bound = d.G.n_wave + (d.G.n_lm + 63) / 64;
+    const Prob Pr = d.Pr;
+    const unsigned long long* obs_mask = d.obs_mask;
+    const double* pose = d.pose;
+    desc_touch(Pr.slot_hdr, Pr.slot_uv, obs_mask, pose);
+    if (skip | ((int)blockIdx.x >= bound)) return;
+    landmarks_body<TRI>(d.G, Pr, obs_mask, pose, d.pw, d.pw_out, d.sel, d.gate, d.info, (int)blockIdx.x);
 }

@@ -136,6 +136,19 @@ class CovInfo(C.Structure):
                 ("cost", C.c_double), ("device_ms", C.c_double)]
 
 
+class BaLandmarkSlot(C.Structure):
+    """rsvio_ba_landmark_slot (48 B): one window's slot of rsvio_ba_batch_triangulate / _check_landmarks."""
+    _fields_ = [("lm_mask", C.c_void_p), ("gate", C.POINTER(LandmarkGate)), ("p_W_out", C.c_void_p),
+                ("info_out", C.c_void_p), ("n_lm", C.c_int32), ("n_ok", C.c_int32), ("status", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class BaCovSlot(C.Structure):
+    """rsvio_ba_cov_slot (80 B): one window's slot of rsvio_ba_batch_covariance."""
+    _fields_ = [("cov_cc", C.c_void_p), ("cov_pose", C.c_void_p), ("lm_idx", C.c_void_p), ("cov_lm", C.c_void_p),
+                ("lm_flags", C.c_void_p), ("n_sel", C.c_int32), ("reserved", C.c_int32), ("info", CovInfo)]
+
+
 # the same record as a numpy dtype (info arrays are filled in place by the library)
 LANDMARK_INFO_DTYPE = [("n_obs", "<i4"), ("flags", "<i4"), ("min_depth", "<f8"), ("max_depth", "<f8"),
                        ("max_sq_error", "<f8")]
@@ -232,6 +245,10 @@ SIG = {
     "rsvio_ba_batch_create": (C.c_int, [P, C.c_int32, C.POINTER(P)]),
     "rsvio_ba_batch_run": (C.c_int, [P, C.POINTER(LmCfg), P]),
     "rsvio_ba_batch_destroy": (None, [P]),
+    "rsvio_ba_batch_run_active": (C.c_int, [P, P, C.POINTER(LmCfg), P]),
+    "rsvio_ba_batch_triangulate": (C.c_int, [P, P, C.POINTER(LandmarkGate), P, C.POINTER(C.c_double)]),
+    "rsvio_ba_batch_check_landmarks": (C.c_int, [P, P, C.POINTER(LandmarkGate), P, C.POINTER(C.c_double)]),
+    "rsvio_ba_batch_covariance": (C.c_int, [P, P, C.c_double, P, C.POINTER(C.c_double)]),
     "rsvio_ba_p2p_export": (C.c_int, [P, C.c_int32, C.POINTER(C.c_uint8), C.c_size_t]),
     "rsvio_ba_attach_p2p": (C.c_int, [P, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     "rsvio_ba_p2p_latency": (C.c_int, [P, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),

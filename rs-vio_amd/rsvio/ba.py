@@ -435,10 +435,130 @@ class BundleBatch:
         check(_lib.load().rsvio_ba_batch_create(arr, len(self.adjusters), C.byref(h)))
         self._h = h
 
-    def run(self, cfg=None):
+    def run(self, cfg=None, active=None):
+        """rsvio_ba_batch_run; with `active` (one truth value per window) rsvio_ba_batch_run_active:
+        only those windows are solved, the entry of any other is None."""
         res = (_lib.BaResult * len(self.adjusters))()
-        check(_lib.load().rsvio_ba_batch_run(self._h, C.byref(cfg or lm_cfg()), res))
-        return list(res)
+        if active is None:
+            check(_lib.load().rsvio_ba_batch_run(self._h, C.byref(cfg or lm_cfg()), res))
+            return list(res)
+        on = self._active(active)
+        check(_lib.load().rsvio_ba_batch_run_active(self._h, ptr(on), C.byref(cfg or lm_cfg()), res))
+        return [r if a else None for r, a in zip(res, on)]
+
+    def _active(self, active):
+        """One byte per window (None: None, every window)."""
+        if active is None:
+            return None
+        on = _c(np.asarray(active).astype(bool), np.uint8).reshape(-1)
+        if on.shape != (len(self.adjusters),):
+            raise ValueError("active: one entry per window of the batch")
+        return on
+
+    def _per_window(self, v, what):
+        """A per-window list from `v`: a list (one entry per window) or one value for all."""
+        if isinstance(v, list):
+            if len(v) != len(self.adjusters):
+                raise ValueError(f"{what}: a list needs one entry per window of the batch")
+            return v
+        return [v] * len(self.adjusters)
+
+    def _landmark_call(self, fn, masks, gates, want_pw, want_info, active):
+        n = len(self.adjusters)
+        on = self._active(active)
+        live = [on is None or bool(on[i]) for i in range(n)]
+        masks, gates = self._per_window(masks, "masks"), self._per_window(gates, "gates")
+        slots = (_lib.BaLandmarkSlot * n)()
+        keep, pws, infos = [], [None] * n, [None] * n
+        for i, a in enumerate(self.adjusters):
+            if not live[i]:
+                continue
+            s = slots[i]
+            s.n_lm = a.n_lm
+            if masks[i] is not None:
+                m = _c(masks[i], np.uint8)
+                if m.shape != (a.n_lm,):
+                    raise ValueError("masks: one byte per landmark of the window")
+                keep.append(m)
+                s.lm_mask = ptr(m)
+            if gates[i] is not None:
+                keep.append(gates[i])
+                s.gate = C.pointer(gates[i])
+            if want_pw:
+                pws[i] = np.empty((a.n_lm, 3))
+                s.p_W_out = ptr(pws[i])
+            if want_info:
+                infos[i] = np.zeros(a.n_lm, _lib.LANDMARK_INFO_DTYPE)
+                s.info_out = ptr(infos[i])
+        ms = C.c_double(0.0)
+        check(fn(self._h, ptr(on), C.byref(landmark_gate()), slots, C.byref(ms)))
+        self.device_ms = ms.value
+        return live, slots, pws, infos
+
+    def triangulate(self, masks=None, gates=None, want=False, active=None):
+        """rsvio_ba_batch_triangulate: BundleAdjuster.triangulate of every active window by one
+        launch.  masks, gates: one value for all windows or a list with one entry per window (None:
+        all landmarks / landmark_gate()).  Returns a list: what BundleAdjuster.triangulate returns
+        per active window (None when want=False: the call only enqueues), None for an inactive one."""
+        live, slots, pws, infos = self._landmark_call(_lib.load().rsvio_ba_batch_triangulate, masks, gates, want, want,
+                                                      active)
+        if not want:
+            return [None] * len(live)
+        return [(pws[i], infos[i], slots[i].n_ok) if live[i] else None for i in range(len(live))]
+
+    def check_landmarks(self, gates=None, active=None):
+        """rsvio_ba_batch_check_landmarks: (info, n_ok) per active window, None for an inactive one."""
+        live, slots, _, infos = self._landmark_call(_lib.load().rsvio_ba_batch_check_landmarks, None, gates, False,
+                                                    True, active)
+        return [(infos[i], slots[i].n_ok) if live[i] else None for i in range(len(live))]
+
+    def covariance(self, landmarks=None, full=False, huber_delta=2.0, active=None):
+        """rsvio_ba_batch_covariance: BundleAdjuster.covariance of every active window by one launch
+        chain.  landmarks: None, True or an index array for all windows, or a list with one such
+        entry per window.  Returns a list of Covariance, None for an inactive window."""
+        n = len(self.adjusters)
+        on = self._active(active)
+        live = [on is None or bool(on[i]) for i in range(n)]
+        sel = self._per_window(landmarks, "landmarks")
+        slots = (_lib.BaCovSlot * n)()
+        bufs = [None] * n
+        for i, a in enumerate(self.adjusters):
+            if not live[i]:
+                continue
+            want = sel[i]
+            if want is None or want is False:
+                idx, n_sel = None, 0
+            elif want is True:
+                idx, n_sel = None, a.n_lm
+            else:
+                idx = _c(np.asarray(want).reshape(-1), np.int32)
+                n_sel = len(idx)
+            pose = np.zeros((a.n_kf, 6, 6))
+            cc = np.zeros(120 * 120) if full else None
+            lm = np.zeros((n_sel, 3, 3)) if n_sel else None
+            flags = np.zeros(n_sel, np.uint8) if n_sel else None
+            bufs[i] = (pose, cc, idx, lm, flags, n_sel)
+            s = slots[i]
+            s.cov_cc, s.cov_pose, s.lm_idx, s.cov_lm, s.lm_flags, s.n_sel = (ptr(cc), ptr(pose), ptr(idx), ptr(lm),
+                                                                             ptr(flags), n_sel)
+        ms = C.c_double(0.0)
+        check(_lib.load().rsvio_ba_batch_covariance(self._h, ptr(on), huber_delta, slots, C.byref(ms)))
+        self.device_ms = ms.value
+        out = [None] * n
+        for i in range(n):
+            if not live[i]:
+                continue
+            pose, cc, idx, lm, flags, n_sel = bufs[i]
+            info = slots[i].info
+            ok = info.status == COV_OK
+            if full and ok:
+                m = 6 * info.n_free
+                cc = cc[:m * m].reshape(m, m).copy()
+            if sel[i] is not None and sel[i] is not False and n_sel == 0:
+                lm, flags = np.zeros((0, 3, 3)), np.zeros(0, np.uint8)
+            out[i] = Covariance(info.status, pose if ok else None, cc if ok else None, lm if ok else None,
+                                flags if ok else None, info.cost, info.device_ms, info.n_free, info.n_singular)
+        return out
 
     def close(self):
         if getattr(self, "_h", None):
@@ -680,3 +800,88 @@ class SlidingWindow:
             res = self.solver.run(fallback_cfg(cfg))
         pose, pw = self.solver.state()
         return self._with_covariance(ids, cfg, self._apply(*self._culled(ids, pose, pw, res)))
+
+
+class WindowBatch:
+    """The keyframe step of several SlidingWindows in one BundleBatch: per window what
+    SlidingWindow.optimize() does -- any mix of landmark_init, cull, covariance and gates -- with
+    the uploads enqueued per window and one batched call each for the triangulation, the solve, the
+    cull gate and the covariance.  Each window keeps its own BundleAdjuster (window.solver)."""
+
+    def __init__(self, windows):
+        self.windows = list(windows)
+        self.batch = BundleBatch([w.solver for w in self.windows])
+
+    def close(self):
+        self.batch.close()
+
+    def optimize(self, cfg=None, active=None) -> list:
+        """SlidingWindow.optimize() of every active window (None: all): a list of its bools, None
+        for an inactive window.  A window the reference's guards skip gives False without a device
+        call; one that is not full raises before anything is done."""
+        W, n = self.windows, len(self.windows)
+        on = [True] * n if active is None else [bool(a) for a in active]
+        if len(on) != n:
+            raise ValueError("active: one entry per window")
+        for w, a in zip(W, on):
+            if a and not w.keyframes:
+                raise RuntimeError("Window is empty")
+            if a and len(w.keyframes) < w.max_frames:
+                raise RuntimeError("Need more keyframes")
+        out, ids, masks = [None] * n, [None] * n, [None] * n
+        live = [False] * n
+        for i, w in enumerate(W):
+            if not on[i]:
+                continue
+            pose7, fixed, p_init, lm, kf, cam, uv, tcb, ids[i] = w.build_problem()
+            if len(lm) < 6 or len(lm) < len(w.keyframes) + len(p_init):
+                w.last_result = None
+                out[i] = False
+                continue
+            w.solver.set_problem(pose7, fixed, p_init, lm, kf, cam, uv, tcb)   # enqueued: no host wait
+            live[i] = True
+            if w.landmark_init == "triangulate":
+                masks[i] = w._new_mask(ids[i])
+        gates = [w.gate for w in W]
+        tri = [m is not None for m in masks]
+        if any(tri):
+            rep = self.batch.triangulate(masks, gates, want=True, active=tri)
+            for i, w in enumerate(W):
+                if tri[i]:
+                    w.last_triangulation = (int(masks[i].sum()), rep[i][2])
+        if not any(live):
+            return out
+        res = self.batch.run(cfg, active=live)
+        state = [None] * n
+        for i, w in enumerate(W):
+            if not live[i]:
+                continue
+            if res[i].status == LINEAR_SOLVE_FAILED:   # the SparseCholesky retry (:326-353), singly
+                w.fallbacks += 1
+                res[i] = w.solver.run(fallback_cfg(cfg))
+            state[i] = w.solver.state()
+        cull = [live[i] and W[i].cull and res[i].status > 0 and len(ids[i]) > 0 for i in range(n)]
+        rep = self.batch.check_landmarks(gates, active=cull) if any(cull) else None
+        for i, w in enumerate(W):
+            if not live[i]:
+                continue
+            pose, pw = state[i]
+            kept = ids[i]
+            if cull[i]:
+                keep = (rep[i][0]["flags"] & LM_OK) != 0
+                kept, pw = np.asarray(kept)[keep], np.asarray(pw).reshape(-1, 3)[keep]
+            out[i] = w._apply(kept, pose, pw, res[i])
+        cov = [live[i] and W[i].covariance and out[i] for i in range(n)]
+        if any(cov):
+            got = self.batch.covariance(landmarks=True, huber_delta=cfg.huber_delta if cfg else 2.0, active=cov)
+            for i, w in enumerate(W):
+                if not cov[i]:
+                    continue
+                c = got[i]
+                if c.status == COV_OK:
+                    seen = c.flags == COV_LM_OK
+                    w.pose_covariance = c.pose
+                    w.landmark_covariance = dict(zip(np.asarray(ids[i])[seen].tolist(), c.landmarks[seen]))
+                else:
+                    w.pose_covariance = w.landmark_covariance = None
+        return out
