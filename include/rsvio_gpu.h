@@ -845,6 +845,59 @@ int rsvio_tracker_device_lists(rsvio_tracker* t, const rsvio_feature** d_l, size
                                const rsvio_feature** d_r, size_t* n_r,
                                const float** d_uv_l, const float** d_uv_r);
 
+/* Stereo gate: an epipolar check on the pairs of every frame, at the frame's end on the device.
+ * StereoPatchTracker::process_frame (feature_tracker.rs:116-187) admits a point when the left ->
+ * right LK track converges and then tracks cam0 and cam1 of that id independently; nothing checks
+ * that the two pixels of an id are views of one 3-D point.  The gate is state of a handle
+ * {mode, max_error, T_Cl_Cr}, off by default; a handle without one behaves exactly as before.
+ *   T_Cl_Cr: row-major 4 x 4, the right camera's pose in the left camera's frame (x_l = R x_r + t).
+ * The host computes E = [t / |t|]x R once in f64 (|t| = sqrt(tx*tx + ty*ty + tz*tz), every entry
+ * of E a left-to-right sum over k = 0, 1, 2).
+ *   At the end of every frame, after the new points were appended and the ids assigned and before
+ * the lists are packed and read back, for every PAIR (an id present in both cameras' maps):
+ *   bearing d from the fused unprojection's stored f32 coordinates (x, y) (what
+ *     rsvio_tracker_undistorted returns) promoted to f64, per camera convention:
+ *       RSVIO_UNPROJ_PLANE  d = (x, y, 1) / sqrt((x*x + y*y) + 1)
+ *       RSVIO_UNPROJ_RAY    s = (1 - x*x) - y*y, d = (x, y, sqrt(s)); s < 0: the pair is invalid
+ *   error   e = |d_l . (E d_r)|, both products left-to-right sums in f64 without contraction
+ *   rejected when a coordinate of either side is NaN (the unprojection failed: invalid, e = NaN),
+ *     s < 0 (invalid), or !(e <= max_error).
+ *   RSVIO_GATE_DROP_RIGHT  a rejected id leaves cam1's map; cam0 keeps tracking it as a mono point
+ *   RSVIO_GATE_DROP_BOTH   it leaves both maps, exactly as rsvio_tracker_remove_ids of that id right
+ *                          after the frame would (its grid cell is free for the next detection)
+ * Ids present in one camera only are never touched; rejected new points still consume their ids;
+ * the overflow flag / RSVIO_ERR_CAPACITY are decided before the gate.  The maps keep ascending ids,
+ * and the affines, the packed lists and the undistorted arrays stay aligned; the counts read back
+ * are the gated ones.  The gate rides in the frame's last launch (single, look-ahead and batched
+ * calls; the handles of a batch may carry different gates): no extra launch, no extra host wait.
+ *   rsvio_tracker_set_stereo_gate: gate NULL or mode RSVIO_GATE_OFF turns it off.
+ * RSVIO_ERR_INVALID_ARG (rsvio_last_error names the reason): no cameras attached, a mode outside
+ * 0..2, max_error not finite or <= 0, a non-finite T, |t| = 0, max |R^T R - I| > 1e-6, a frame in
+ * flight.  rsvio_tracker_set_cameras(t, NULL, NULL) is refused while a gate is set.
+ *   rsvio_tracker_gate_report: the last collected frame (a batch's frame counts as collected):
+ * n_pairs before the gate, n_rejected, n_invalid (a subset of the rejected); the rejected ids
+ * ascending, each with its e (NaN for an invalid pair); *n = n_rejected.  cap < *n truncates and
+ * returns RSVIO_ERR_CAPACITY -- except ids_out = err_out = NULL with cap = 0, which asks for the
+ * counts alone.  Zeros with the gate off.  The counters travel with the frame's counts read-back;
+ * the list is fetched by this call (the collected frame's own buffer: a frame submitted since
+ * writes another).  counts, ids_out, err_out and n may each be NULL.
+ *   rsvio_stereo_gate_lists: the same device function on two arbitrary lists with ascending ids
+ * (host buffers, current device; uv: n x 2 f32 stored coordinates; any lengths): keep_l / keep_r
+ * 0 or 1 per entry (keep_l all 1 under DROP_RIGHT), err_r[j] = e of right entry j (NaN: unpaired or
+ * invalid).  mode must be DROP_RIGHT or DROP_BOTH; ids not strictly ascending within a list, a
+ * convention other than RSVIO_UNPROJ_*, or a gate set_stereo_gate would refuse:
+ * RSVIO_ERR_INVALID_ARG, checked before any device call.  counts may be NULL. */
+enum { RSVIO_GATE_OFF = 0, RSVIO_GATE_DROP_RIGHT = 1, RSVIO_GATE_DROP_BOTH = 2 };
+typedef struct { int32_t mode, reserved; double max_error; double T_Cl_Cr[16]; } rsvio_stereo_gate;   /* 144 bytes */
+typedef struct { int32_t n_pairs, n_rejected, n_invalid, reserved; } rsvio_gate_counts;               /* 16 bytes */
+int rsvio_tracker_set_stereo_gate(rsvio_tracker* t, const rsvio_stereo_gate* gate);
+int rsvio_tracker_gate_report(rsvio_tracker* t, rsvio_gate_counts* counts,
+                              uint64_t* ids_out, double* err_out, size_t cap, size_t* n);
+int rsvio_stereo_gate_lists(const rsvio_stereo_gate* gate, int32_t convention_l, int32_t convention_r,
+                            const uint64_t* ids_l, const float* uv_l, size_t n_l,
+                            const uint64_t* ids_r, const float* uv_r, size_t n_r,
+                            uint8_t* keep_l, uint8_t* keep_r, double* err_r, rsvio_gate_counts* counts);
+
 #ifdef __cplusplus
 }
 #endif

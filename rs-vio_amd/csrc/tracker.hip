@@ -11,7 +11,9 @@
 //   K2 ONE launch: temporal track cam0 + cam1, and the stereo track cam0 -> cam1 of every
 //      cell's corner (one job per cell, cells without a corner masked)   lk_track.hip
 //   Ka compact the survivors, bin them, append the corners of the cells holding no surviving
-//      cam0 track in cell scan order with consecutive ids, pack (+ unprojection) (1 workgroup)
+//      cam0 track in cell scan order with consecutive ids, pack (+ unprojection) (1 workgroup);
+//      with a stereo gate set on the handle (tracker_gate.hpp), the epipolar check of the frame's
+//      pairs and the compaction of the rejected ones, between the append and the packing
 // The reference detects only in the cells its surviving tracks leave empty and then tracks those
 // corners; a cell's corner and its stereo track depend on nothing but the cell and the images,
 // so detecting and tracking every cell up front and dropping the occupied ones afterwards gives
@@ -104,6 +106,8 @@ struct CamPair {
     int on;
 };
 
+#include "tracker_gate.hpp"
+
 // The end of process_frame in one workgroup: (1) the surviving temporal tracks of each camera
 // compacted in order from the tracker's output (at, valid) into the track map (feature_tracker.rs
 // :131-141 -- failed tracks are dropped, the map keeps ascending ids); (2) the corners of the
@@ -111,6 +115,9 @@ struct CamPair {
 // appended in cell scan order with consecutive ids (feature_tracker.rs:143-170, canonical order); (3) get_track_points packing, with the
 // Frame::add_{left,right}_feature unprojection fused (frame.rs:118-119,131-132).  tracked = 0
 // (first frame): the maps are taken as they are (counts = n0, n1).
+// GATE: the stereo gate (tracker_gate.hpp) between (2) and (3), on the stored coordinates of (3)'s
+// unprojection, which then runs before it; GATE = false is the kernel without any of it.
+template <bool GATE>
 __device__ __forceinline__ void append_pack(
     const GridGeom& G, int* __restrict__ bins, int n0, int n1, int tracked, const float* __restrict__ at0, const float* __restrict__ at1,
     const uint8_t* __restrict__ tv0, const uint8_t* __restrict__ tv1, uint64_t* __restrict__ ids_tmp,
@@ -119,7 +126,7 @@ __device__ __forceinline__ void append_pack(
     float* __restrict__ map_aff1, uint64_t* __restrict__ ids0, uint64_t* __restrict__ ids1,
     int* __restrict__ counts, unsigned long long* __restrict__ last_id, int capacity,
     rsvio_feature* __restrict__ out0, rsvio_feature* __restrict__ out1, int* __restrict__ overflow,
-    const CamPair& cams, float2* __restrict__ und0, float2* __restrict__ und1) {
+    const CamPair& cams, float2* __restrict__ und0, float2* __restrict__ und1, const GateDev& gate) {
     __shared__ int sh[1024];
     const int tid = threadIdx.x;
     int cnt[2] = {n0, n1};
@@ -191,12 +198,32 @@ __device__ __forceinline__ void append_pack(
         ++pos;
     }
     __syncthreads();
-    const int m0 = c0 + admit, m1 = c1 + admit;
+    int m0 = c0 + admit, m1 = c1 + admit;
     if (tid == 0) {
         counts[0] = m0;
         counts[1] = m1;
         *last_id = base + (unsigned long long)admit;
         *overflow = total > admit ? 1 : 0;
+    }
+    bool gated = false;  // the stored coordinates are in place (and compacted) before the packing
+    if constexpr (GATE) {
+        gated = gate.mode != RSVIO_GATE_OFF && cams.on;  // (block-uniform)
+        if (gated) {
+            for (int j = tid; j < m0 + m1; j += blockDim.x) {
+                const int c = j < m0 ? 0 : 1;
+                const int i = c == 0 ? j : j - m0;
+                const float* a = (c == 0 ? map_aff0 : map_aff1) + 6 * i;
+                const Undist u = unproject_one(cams.cam[c], a[4], a[5]);
+                (c == 0 ? und0 : und1)[i] = make_float2(u.x, u.y);
+            }
+            __syncthreads();
+            stereo_gate(gate, cams.cam[0].convention, cams.cam[1].convention, capacity, ids0, ids1, map_aff0,
+                        map_aff1, und0, und1, ids_tmp, sh, m0, m1);
+            if (tid == 0) {  // the gated counts are the ones read back
+                counts[0] = m0;
+                counts[1] = m1;
+            }
+        }
     }
     // get_track_points packing, both cameras spread over the block
     for (int j = tid; j < m0 + m1; j += blockDim.x) {
@@ -207,7 +234,7 @@ __device__ __forceinline__ void append_pack(
         f.id = (c == 0 ? ids0 : ids1)[i]; f.x = a[4]; f.y = a[5];
         f.r[0] = a[0]; f.r[1] = a[1]; f.r[2] = a[2]; f.r[3] = a[3];
         (c == 0 ? out0 : out1)[i] = f;
-        if (cams.on) {
+        if (cams.on && !(GATE && gated)) {
             const Undist u = unproject_one(cams.cam[c], f.x, f.y);
             (c == 0 ? und0 : und1)[i] = make_float2(u.x, u.y);
         }
@@ -225,9 +252,24 @@ __global__ __launch_bounds__(1024) void append_pack_kernel(
     int* __restrict__ counts, unsigned long long* __restrict__ last_id, int capacity,
     rsvio_feature* __restrict__ out0, rsvio_feature* __restrict__ out1, int* __restrict__ overflow,
     CamPair cams, float2* __restrict__ und0, float2* __restrict__ und1) {
-    append_pack(G, bins, n0, n1, tracked, at0, at1, tv0, tv1, ids_tmp, cell_pt, n_cells, new_aff0, new_aff1,
-                new_valid, map_aff0, map_aff1, ids0, ids1, counts, last_id, capacity, out0, out1, overflow, cams,
-                und0, und1);
+    append_pack<false>(G, bins, n0, n1, tracked, at0, at1, tv0, tv1, ids_tmp, cell_pt, n_cells, new_aff0, new_aff1,
+                       new_valid, map_aff0, map_aff1, ids0, ids1, counts, last_id, capacity, out0, out1, overflow,
+                       cams, und0, und1, GateDev{});
+}
+
+// The same launch for a handle with a stereo gate set
+__global__ __launch_bounds__(1024) void append_pack_gate_kernel(
+    GridGeom G, int* __restrict__ bins, int n0, int n1, int tracked, const float* __restrict__ at0, const float* __restrict__ at1,
+    const uint8_t* __restrict__ tv0, const uint8_t* __restrict__ tv1, uint64_t* __restrict__ ids_tmp,
+    const int4* __restrict__ cell_pt, int n_cells, const float* __restrict__ new_aff0,
+    const float* __restrict__ new_aff1, const uint8_t* __restrict__ new_valid, float* __restrict__ map_aff0,
+    float* __restrict__ map_aff1, uint64_t* __restrict__ ids0, uint64_t* __restrict__ ids1,
+    int* __restrict__ counts, unsigned long long* __restrict__ last_id, int capacity,
+    rsvio_feature* __restrict__ out0, rsvio_feature* __restrict__ out1, int* __restrict__ overflow,
+    CamPair cams, float2* __restrict__ und0, float2* __restrict__ und1, GateDev gate) {
+    append_pack<true>(G, bins, n0, n1, tracked, at0, at1, tv0, tv1, ids_tmp, cell_pt, n_cells, new_aff0, new_aff1,
+                      new_valid, map_aff0, map_aff1, ids0, ids1, counts, last_id, capacity, out0, out1, overflow,
+                      cams, und0, und1, gate);
 }
 
 // StereoPatchTracker::remove_id (feature_tracker.rs:201-206)
@@ -320,6 +362,40 @@ struct Tracker {
     bool inflight = false;          // a frame was submitted and not yet collected
     size_t bnd[2] = {0, 0};         // the list bounds the submit's copies covered
     hipEvent_t ev_done = nullptr;   // after the submitted frame's read-back copies
+    // the stereo gate (rsvio_tracker_set_stereo_gate); its buffers are allocated when one is first set
+    rsvio_stereo_gate gate{};       // mode RSVIO_GATE_OFF: none
+    double gate_E[9] = {};          // [t / |t|]x R of gate.T_Cl_Cr
+    DevBuf<uint8_t> gate_keep;      // 2 x cap keep flags
+    DevBuf<double> gate_err;        // cap: e of every cam1 entry
+    DevBuf<float> gate_aff;         // 2 x cap x 6 compaction scratch
+    DevBuf<uint64_t> rep_ids;       // the rejected ids, one list per output slot (2 x cap): gate_report()
+    DevBuf<double> rep_err;         // reads the collected frame's, the next frame writes the other
+    rsvio_gate_counts rep_counts{}; // of the last collected frame
+
+    bool gated() const { return gate.mode != RSVIO_GATE_OFF; }
+    GateDev gate_dev(int slot) {
+        GateDev g{};
+        g.mode = gate.mode;
+        g.max_error = gate.max_error;
+        for (int i = 0; i < 9; ++i) g.E[i] = gate_E[i];
+        g.keep = gate_keep.p;
+        g.err = gate_err.p;
+        g.tmp_aff = gate_aff.p;
+        g.tmp_und = tmp_und.p;
+        g.rep_ids = rep_ids.p ? rep_ids.p + (size_t)slot * cap : nullptr;
+        g.rep_err = rep_err.p ? rep_err.p + (size_t)slot * cap : nullptr;
+        g.counters = counts.p + 4;
+        return g;
+    }
+    // the frame's gate counters as read back with its counts (fetch, the batch)
+    void set_report(const int* c) {
+        rep_counts = rsvio_gate_counts{};
+        if (gated()) {
+            rep_counts.n_pairs = c[0];
+            rep_counts.n_rejected = c[1];
+            rep_counts.n_invalid = c[2];
+        }
+    }
 
     uint8_t* pyr(int slot, int cam) { return d_pyr.p + (size_t)(2 * slot + cam) * pyr_bytes; }
 
@@ -347,16 +423,16 @@ struct Tracker {
         new_aff.alloc((size_t)n_cells * 6);
         new_aff1.alloc((size_t)n_cells * 6);
         new_valid.alloc(n_cells);
-        counts.alloc(2);
+        counts.alloc(8);   // {n0, n1, -, -} and the stereo gate's {n_pairs, n_rejected, n_invalid, 0}
         bins.alloc((size_t)G.bin_rows * G.bin_cols);
         overflow.alloc(1);
         cell_pt.alloc(n_cells);
         last_id.alloc(1);
         out.alloc((size_t)4 * cap);
-        h_counts.alloc(4);
+        h_counts.alloc(8);  // {n0, n1, overflow, -} and the gate's counters
         RSVIO_HIP(hipEventCreateWithFlags(&ev_done, hipEventDisableTiming));
         h_out.alloc((size_t)2 * cap);
-        RSVIO_HIP(hipMemsetAsync(counts.p, 0, sizeof(int) * 2, stream));
+        RSVIO_HIP(hipMemsetAsync(counts.p, 0, sizeof(int) * 8, stream));
         RSVIO_HIP(hipMemsetAsync(last_id.p, 0, sizeof(unsigned long long), stream));
         RSVIO_HIP(hipMemsetAsync(overflow.p, 0, sizeof(int), stream));
         RSVIO_HIP(hipStreamSynchronize(stream));
@@ -404,11 +480,18 @@ struct Tracker {
             L.nb = b + 1;
             enqueue_track(L, stream);
         }
-        hipLaunchKernelGGL(append_pack_kernel, dim3(1), dim3(1024), 0, stream, G, bins.p, host_count[0],
-                           host_count[1], has_prev ? 1 : 0, taff(0), taff(1), valid.p, valid.p + cap, ids_tmp.p,
-                           cell_pt.p, n_cells, new_aff.p, new_aff1.p, new_valid.p, maff(0), maff(1), mid(0), mid(1),
-                           counts.p, last_id.p, cap, outp(wslot, 0), outp(wslot, 1), overflow.p, cams,
-                           undp(wslot, 0), undp(wslot, 1));
+        if (!gated())
+            hipLaunchKernelGGL(append_pack_kernel, dim3(1), dim3(1024), 0, stream, G, bins.p, host_count[0],
+                               host_count[1], has_prev ? 1 : 0, taff(0), taff(1), valid.p, valid.p + cap, ids_tmp.p,
+                               cell_pt.p, n_cells, new_aff.p, new_aff1.p, new_valid.p, maff(0), maff(1), mid(0), mid(1),
+                               counts.p, last_id.p, cap, outp(wslot, 0), outp(wslot, 1), overflow.p, cams,
+                               undp(wslot, 0), undp(wslot, 1));
+        else
+            hipLaunchKernelGGL(append_pack_gate_kernel, dim3(1), dim3(1024), 0, stream, G, bins.p, host_count[0],
+                               host_count[1], has_prev ? 1 : 0, taff(0), taff(1), valid.p, valid.p + cap, ids_tmp.p,
+                               cell_pt.p, n_cells, new_aff.p, new_aff1.p, new_valid.p, maff(0), maff(1), mid(0), mid(1),
+                               counts.p, last_id.p, cap, outp(wslot, 0), outp(wslot, 1), overflow.p, cams,
+                               undp(wslot, 0), undp(wslot, 1), gate_dev(wslot));
         RSVIO_HIP(hipGetLastError());
         cur = nxt;
         has_prev = true;
@@ -437,7 +520,8 @@ struct Tracker {
         enqueue_frame(d_left, d_right);
         bnd[0] = std::min((size_t)cap, (size_t)host_count[0] + (size_t)n_cells);
         bnd[1] = std::min((size_t)cap, (size_t)host_count[1] + (size_t)n_cells);
-        RSVIO_HIP(hipMemcpyAsync(h_counts.p, counts.p, sizeof(int) * 2, hipMemcpyDeviceToHost, stream));
+        // (with a gate its counters ride in the counts' copy; the overflow flag lands on top of it)
+        RSVIO_HIP(hipMemcpyAsync(h_counts.p, counts.p, sizeof(int) * (gated() ? 8 : 2), hipMemcpyDeviceToHost, stream));
         RSVIO_HIP(hipMemcpyAsync(h_counts.p + 2, overflow.p, sizeof(int), hipMemcpyDeviceToHost, stream));
         copy_lists(wslot, 0, bnd[0], 0, bnd[1]);
         RSVIO_HIP(hipEventRecord(ev_done, stream));
@@ -459,6 +543,7 @@ struct Tracker {
         const size_t bl = bnd[0], br = bnd[1];
         host_count[0] = h_counts.p[0];
         host_count[1] = h_counts.p[1];
+        set_report(h_counts.p + 4);
         const size_t ml = std::min((size_t)host_count[0], (size_t)cap), mr = std::min((size_t)host_count[1], (size_t)cap);
         coll_n[0] = (int)ml;
         coll_n[1] = (int)mr;
@@ -700,6 +785,8 @@ int rsvio_tracker_set_cameras(rsvio_tracker* t, const rsvio_camera* left, const 
         T.require_collected("rsvio_tracker_set_cameras");
         RSVIO_HIP(hipStreamSynchronize(T.stream));
         if (!left) {
+            if (T.gated())
+                throw std::invalid_argument("rsvio_tracker_set_cameras: a stereo gate is set (turn it off first)");
             T.cams.on = 0;
             T.last_n[0] = T.last_n[1] = 0;
             return (int)RSVIO_OK;
@@ -728,6 +815,215 @@ int rsvio_tracker_undistorted(rsvio_tracker* t, float* out_l, size_t cap_l, floa
     std::memcpy(out_l, T.hund(T.rslot, 0), T.last_n[0] * sizeof(float2));
     std::memcpy(out_r, T.hund(T.rslot, 1), T.last_n[1] * sizeof(float2));
     return RSVIO_OK;
+}
+
+namespace {
+// The checks of a gate that need no handle, and E = [t / |t|]x R: f64, every entry a left-to-right
+// sum over k = 0, 1, 2.  Throws std::invalid_argument naming the reason.
+static void gate_essential(const char* who, const rsvio_stereo_gate& g, double E[9]) {
+    const std::string at = std::string(who) + ": ";
+    if (!(std::isfinite(g.max_error) && g.max_error > 0.0))
+        throw std::invalid_argument(at + "max_error must be finite and > 0");
+    for (int i = 0; i < 16; ++i)
+        if (!std::isfinite(g.T_Cl_Cr[i])) throw std::invalid_argument(at + "T_Cl_Cr is not finite");
+    const double* T = g.T_Cl_Cr;
+    const double R[3][3] = {{T[0], T[1], T[2]}, {T[4], T[5], T[6]}, {T[8], T[9], T[10]}};
+    const double tx = T[3], ty = T[7], tz = T[11];
+    const double nt = std::sqrt(tx * tx + ty * ty + tz * tz);
+    if (!(nt > 0.0) || !std::isfinite(nt)) throw std::invalid_argument(at + "the translation of T_Cl_Cr is zero");
+    double dev = 0.0;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const double v = R[0][i] * R[0][j] + R[1][i] * R[1][j] + R[2][i] * R[2][j];
+            dev = std::max(dev, std::fabs(v - (i == j ? 1.0 : 0.0)));
+        }
+    if (!(dev <= 1e-6)) throw std::invalid_argument(at + "the rotation of T_Cl_Cr is not orthonormal (|R^T R - I| > 1e-6)");
+    const double h[3] = {tx / nt, ty / nt, tz / nt};
+    const double S[3][3] = {{0.0, -h[2], h[1]}, {h[2], 0.0, -h[0]}, {-h[1], h[0], 0.0}};
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) E[3 * i + j] = S[i][0] * R[0][j] + S[i][1] * R[1][j] + S[i][2] * R[2][j];
+}
+}  // namespace
+
+int rsvio_tracker_set_stereo_gate(rsvio_tracker* t, const rsvio_stereo_gate* gate) {
+    if (!t) return RSVIO_ERR_INVALID_ARG;
+    return guarded([&] {
+        auto& T = t->t;
+        const char* who = "rsvio_tracker_set_stereo_gate";
+        if (gate && (gate->mode < RSVIO_GATE_OFF || gate->mode > RSVIO_GATE_DROP_BOTH))
+            throw std::invalid_argument(std::string(who) + ": mode must be RSVIO_GATE_OFF, _DROP_RIGHT or _DROP_BOTH");
+        T.require_collected(who);
+        if (!gate || gate->mode == RSVIO_GATE_OFF) {
+            T.gate = rsvio_stereo_gate{};
+            T.rep_counts = rsvio_gate_counts{};
+            return (int)RSVIO_OK;
+        }
+        if (!T.cams.on) throw std::invalid_argument(std::string(who) + ": no cameras attached (rsvio_tracker_set_cameras)");
+        double E[9];
+        gate_essential(who, *gate, E);
+        RSVIO_HIP(hipSetDevice(T.P.device));
+        RSVIO_HIP(hipStreamSynchronize(T.stream));
+        if (!T.gate_keep.p) {
+            T.gate_keep.alloc((size_t)2 * T.cap);
+            T.gate_err.alloc((size_t)T.cap);
+            T.gate_aff.alloc((size_t)2 * T.cap * 6);
+            T.rep_ids.alloc((size_t)2 * T.cap);
+            T.rep_err.alloc((size_t)2 * T.cap);
+        }
+        if (!T.gated()) T.rep_counts = rsvio_gate_counts{};  // no gated frame was collected yet
+        T.gate = *gate;
+        T.gate.reserved = 0;
+        std::memcpy(T.gate_E, E, sizeof(E));
+        return (int)RSVIO_OK;
+    });
+}
+
+int rsvio_tracker_gate_report(rsvio_tracker* t, rsvio_gate_counts* counts, uint64_t* ids_out, double* err_out,
+                              size_t cap, size_t* n) {
+    if (!t) return RSVIO_ERR_INVALID_ARG;
+    return guarded([&] {
+        auto& T = t->t;
+        const rsvio_gate_counts c = T.gated() ? T.rep_counts : rsvio_gate_counts{};
+        if (counts) *counts = c;
+        const size_t m = (size_t)std::max(c.n_rejected, 0);
+        if (n) *n = m;
+        if (!ids_out && !err_out && cap == 0) return (int)RSVIO_OK;  // the counts alone
+        const size_t k = std::min(m, cap);
+        if (k) {
+            // the collected frame's slot was complete when its frame was collected; a frame submitted
+            // since writes the other slot on the handle's stream, which this copy does not wait for
+            RSVIO_HIP(hipSetDevice(T.P.device));
+            if (ids_out)
+                RSVIO_HIP(hipMemcpy(ids_out, T.rep_ids.p + (size_t)T.rslot * T.cap, k * sizeof(uint64_t),
+                                    hipMemcpyDeviceToHost));
+            if (err_out)
+                RSVIO_HIP(hipMemcpy(err_out, T.rep_err.p + (size_t)T.rslot * T.cap, k * sizeof(double),
+                                    hipMemcpyDeviceToHost));
+        }
+        if (cap < m) {
+            rsvio::set_last_error("rsvio_tracker_gate_report: more rejected ids than the output capacity (truncated)");
+            return (int)RSVIO_ERR_CAPACITY;
+        }
+        return (int)RSVIO_OK;
+    });
+}
+
+int rsvio_stereo_gate_lists(const rsvio_stereo_gate* gate, int32_t convention_l, int32_t convention_r,
+                            const uint64_t* ids_l, const float* uv_l, size_t n_l, const uint64_t* ids_r,
+                            const float* uv_r, size_t n_r, uint8_t* keep_l, uint8_t* keep_r, double* err_r,
+                            rsvio_gate_counts* counts) {
+    if (!gate || (n_l && (!ids_l || !uv_l || !keep_l)) || (n_r && (!ids_r || !uv_r || !keep_r || !err_r)))
+        return RSVIO_ERR_INVALID_ARG;
+    return guarded([&] {
+        const char* who = "rsvio_stereo_gate_lists";
+        const std::string at = std::string(who) + ": ";
+        if (gate->mode != RSVIO_GATE_DROP_RIGHT && gate->mode != RSVIO_GATE_DROP_BOTH)
+            throw std::invalid_argument(at + "mode must be RSVIO_GATE_DROP_RIGHT or RSVIO_GATE_DROP_BOTH");
+        for (int32_t cv : {convention_l, convention_r})
+            if (cv != RSVIO_UNPROJ_PLANE && cv != RSVIO_UNPROJ_RAY)
+                throw std::invalid_argument(at + "convention must be RSVIO_UNPROJ_PLANE or RSVIO_UNPROJ_RAY");
+        if (n_l > (size_t)1 << 30 || n_r > (size_t)1 << 30) throw std::invalid_argument(at + "list too long");
+        double E[9];
+        gate_essential(who, *gate, E);
+        for (size_t i = 1; i < n_l; ++i)
+            if (!(ids_l[i - 1] < ids_l[i])) throw std::invalid_argument(at + "left ids are not strictly ascending");
+        for (size_t i = 1; i < n_r; ++i)
+            if (!(ids_r[i - 1] < ids_r[i])) throw std::invalid_argument(at + "right ids are not strictly ascending");
+        const size_t al = std::max(n_l, (size_t)1), ar = std::max(n_r, (size_t)1);
+        rsvio::DevBuf<uint64_t> d_il(al), d_ir(ar);
+        rsvio::DevBuf<float2> d_ul(al), d_ur(ar);
+        rsvio::DevBuf<uint8_t> d_kl(al), d_kr(ar);
+        rsvio::DevBuf<double> d_err(ar), d_E(9);
+        rsvio::DevBuf<int> d_cnt(4);
+        if (n_l) {
+            RSVIO_HIP(hipMemcpy(d_il.p, ids_l, n_l * sizeof(uint64_t), hipMemcpyHostToDevice));
+            RSVIO_HIP(hipMemcpy(d_ul.p, uv_l, n_l * sizeof(float2), hipMemcpyHostToDevice));
+        }
+        if (n_r) {
+            RSVIO_HIP(hipMemcpy(d_ir.p, ids_r, n_r * sizeof(uint64_t), hipMemcpyHostToDevice));
+            RSVIO_HIP(hipMemcpy(d_ur.p, uv_r, n_r * sizeof(float2), hipMemcpyHostToDevice));
+        }
+        RSVIO_HIP(hipMemcpy(d_E.p, E, sizeof(E), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(rsvio::stereo_gate_lists_kernel, dim3(1), dim3(1024), 0, nullptr, (int)gate->mode,
+                           gate->max_error, d_E.p, (int)convention_l, (int)convention_r, d_il.p, d_ul.p, (int)n_l, d_ir.p,
+                           d_ur.p, (int)n_r, d_kl.p, d_kr.p, d_err.p, d_cnt.p);
+        RSVIO_HIP(hipGetLastError());
+        if (n_l) RSVIO_HIP(hipMemcpy(keep_l, d_kl.p, n_l, hipMemcpyDeviceToHost));
+        if (n_r) {
+            RSVIO_HIP(hipMemcpy(keep_r, d_kr.p, n_r, hipMemcpyDeviceToHost));
+            RSVIO_HIP(hipMemcpy(err_r, d_err.p, n_r * sizeof(double), hipMemcpyDeviceToHost));
+        }
+        int c[4] = {0, 0, 0, 0};
+        RSVIO_HIP(hipMemcpy(c, d_cnt.p, sizeof(c), hipMemcpyDeviceToHost));  // (waits for the kernel)
+        if (counts) *counts = rsvio_gate_counts{c[0], c[1], c[2], 0};
+        return (int)RSVIO_OK;
+    });
+}
+
+// Diagnostic (tests; not in the header): the frame end's gate -- flags, compaction of ids, affines
+// (n x 6) and stored coordinates, report -- on two given maps of any length, in place on the host
+// arrays: *n_l / *n_r in: the lengths, out: the gated lengths; rep_ids / rep_err: n_r entries.
+int rsvio_dbg_stereo_gate_frame(const rsvio_stereo_gate* gate, int32_t convention_l, int32_t convention_r,
+                                uint64_t* ids_l, float* uv_l, float* aff_l, size_t* n_l, uint64_t* ids_r, float* uv_r,
+                                float* aff_r, size_t* n_r, uint64_t* rep_ids, double* rep_err,
+                                rsvio_gate_counts* counts) {
+    if (!gate || !n_l || !n_r || !counts || (*n_l && (!ids_l || !uv_l || !aff_l)) ||
+        (*n_r && (!ids_r || !uv_r || !aff_r || !rep_ids || !rep_err)) || *n_l > (size_t)1 << 24 ||
+        *n_r > (size_t)1 << 24)
+        return RSVIO_ERR_INVALID_ARG;
+    return guarded([&] {
+        if (gate->mode != RSVIO_GATE_DROP_RIGHT && gate->mode != RSVIO_GATE_DROP_BOTH)
+            throw std::invalid_argument("rsvio_dbg_stereo_gate_frame: mode must be a DROP mode");
+        rsvio::GateDev g{};
+        gate_essential("rsvio_dbg_stereo_gate_frame", *gate, g.E);
+        const size_t nl = *n_l, nr = *n_r, cap = std::max(std::max(nl, nr), (size_t)1);
+        rsvio::DevBuf<uint64_t> d_ids(2 * cap), d_tmp(2 * cap), d_rep(cap);
+        rsvio::DevBuf<float> d_aff(2 * cap * 6), d_taff(2 * cap * 6);
+        rsvio::DevBuf<float2> d_und(2 * cap), d_tund(cap);
+        rsvio::DevBuf<uint8_t> d_keep(2 * cap);
+        rsvio::DevBuf<double> d_err(cap), d_rerr(cap);
+        rsvio::DevBuf<int> d_cnt(4), d_n(2);
+        const uint64_t* hi[2] = {ids_l, ids_r};
+        const float* hu[2] = {uv_l, uv_r};
+        const float* ha[2] = {aff_l, aff_r};
+        const size_t hn[2] = {nl, nr};
+        for (int c = 0; c < 2; ++c) {
+            if (!hn[c]) continue;
+            RSVIO_HIP(hipMemcpy(d_ids.p + c * cap, hi[c], hn[c] * sizeof(uint64_t), hipMemcpyHostToDevice));
+            RSVIO_HIP(hipMemcpy(d_und.p + c * cap, hu[c], hn[c] * sizeof(float2), hipMemcpyHostToDevice));
+            RSVIO_HIP(hipMemcpy(d_aff.p + c * cap * 6, ha[c], hn[c] * 6 * sizeof(float), hipMemcpyHostToDevice));
+        }
+        g.mode = gate->mode;
+        g.max_error = gate->max_error;
+        g.keep = d_keep.p; g.err = d_err.p; g.tmp_aff = d_taff.p; g.tmp_und = d_tund.p;
+        g.rep_ids = d_rep.p; g.rep_err = d_rerr.p; g.counters = d_cnt.p;
+        hipLaunchKernelGGL(rsvio::stereo_gate_frame_kernel, dim3(1), dim3(1024), 0, nullptr, g, (int)convention_l,
+                           (int)convention_r, (int)cap, d_ids.p, d_ids.p + cap, d_aff.p, d_aff.p + cap * 6, d_und.p,
+                           d_und.p + cap, d_tmp.p, (int)nl, (int)nr, d_n.p);
+        RSVIO_HIP(hipGetLastError());
+        int m[2] = {0, 0}, c4[4] = {0, 0, 0, 0};
+        RSVIO_HIP(hipMemcpy(m, d_n.p, sizeof(m), hipMemcpyDeviceToHost));
+        RSVIO_HIP(hipMemcpy(c4, d_cnt.p, sizeof(c4), hipMemcpyDeviceToHost));
+        uint64_t* oi[2] = {ids_l, ids_r};
+        float* ou[2] = {uv_l, uv_r};
+        float* oa[2] = {aff_l, aff_r};
+        for (int c = 0; c < 2; ++c) {
+            const size_t k = std::min((size_t)std::max(m[c], 0), hn[c]);
+            if (!k) continue;
+            RSVIO_HIP(hipMemcpy(oi[c], d_ids.p + c * cap, k * sizeof(uint64_t), hipMemcpyDeviceToHost));
+            RSVIO_HIP(hipMemcpy(ou[c], d_und.p + c * cap, k * sizeof(float2), hipMemcpyDeviceToHost));
+            RSVIO_HIP(hipMemcpy(oa[c], d_aff.p + c * cap * 6, k * 6 * sizeof(float), hipMemcpyDeviceToHost));
+        }
+        const size_t nrej = std::min((size_t)std::max(c4[1], 0), nr);
+        if (nrej) {
+            RSVIO_HIP(hipMemcpy(rep_ids, d_rep.p, nrej * sizeof(uint64_t), hipMemcpyDeviceToHost));
+            RSVIO_HIP(hipMemcpy(rep_err, d_rerr.p, nrej * sizeof(double), hipMemcpyDeviceToHost));
+        }
+        *n_l = (size_t)std::max(m[0], 0);
+        *n_r = (size_t)std::max(m[1], 0);
+        *counts = rsvio_gate_counts{c4[0], c4[1], c4[2], 0};
+        return (int)RSVIO_OK;
+    });
 }
 
 int rsvio_tracker_remove_ids(rsvio_tracker* t, const uint64_t* ids, size_t n) {

@@ -44,19 +44,20 @@ struct BatchSlot {
     int* overflow;
     float2* und0;
     float2* und1;
-    int* rb_head;          // {n_l, n_r, overflow, 0}
+    int* rb_head;          // {n_l, n_r, overflow, 0, gate: n_pairs, n_rejected, n_invalid, 0}
     rsvio_feature* rb[2];  // bnd[c] entries each
     float2* rbu[2];        // likewise, with cameras
     int bnd[2];            // the host-known bound of each list (submit's)
     CamPair cams;
+    GateDev gate;          // the handle's stereo gate (mode OFF: none); read by the gate launch only
 };
 
 __global__ __launch_bounds__(1024) void append_pack_batch_kernel(GridGeom G, int n_cells,
                                                                  const BatchSlot* __restrict__ slots) {
     const BatchSlot& d = slots[blockIdx.x];
-    append_pack(G, d.bins, d.n0, d.n1, d.tracked, d.at0, d.at1, d.tv0, d.tv1, d.ids_tmp, d.cell_pt, n_cells,
-                d.new_aff0, d.new_aff1, d.new_valid, d.map_aff0, d.map_aff1, d.ids0, d.ids1, d.counts, d.last_id,
-                d.capacity, d.out0, d.out1, d.overflow, d.cams, d.und0, d.und1);
+    append_pack<false>(G, d.bins, d.n0, d.n1, d.tracked, d.at0, d.at1, d.tv0, d.tv1, d.ids_tmp, d.cell_pt, n_cells,
+                       d.new_aff0, d.new_aff1, d.new_valid, d.map_aff0, d.map_aff1, d.ids0, d.ids1, d.counts,
+                       d.last_id, d.capacity, d.out0, d.out1, d.overflow, d.cams, d.und0, d.und1, GateDev{});
     __syncthreads();  // the lists and counts are this workgroup's own writes
     const int m0 = d.counts[0], m1 = d.counts[1];
     if (threadIdx.x == 0) {
@@ -65,6 +66,33 @@ __global__ __launch_bounds__(1024) void append_pack_batch_kernel(GridGeom G, int
         d.rb_head[2] = *d.overflow;
         d.rb_head[3] = 0;
     }
+    const int k0 = min(m0, d.bnd[0]), k1 = min(m1, d.bnd[1]);
+    for (int j = threadIdx.x; j < k0 + k1; j += blockDim.x) {
+        const int c = j < k0 ? 0 : 1;
+        const int i = c == 0 ? j : j - k0;
+        d.rb[c][i] = (c == 0 ? d.out0 : d.out1)[i];
+        if (d.cams.on) d.rbu[c][i] = (c == 0 ? d.und0 : d.und1)[i];
+    }
+}
+
+// The same launch when some handle of the batch has a stereo gate set: each workgroup follows its
+// own slot's gate, and the gate's counters join the head.  (A launch of its own, not a template
+// over the one above: that one stays the code it was, instruction for instruction.)
+__global__ __launch_bounds__(1024) void append_pack_batch_gate_kernel(GridGeom G, int n_cells,
+                                                                      const BatchSlot* __restrict__ slots) {
+    const BatchSlot& d = slots[blockIdx.x];
+    append_pack<true>(G, d.bins, d.n0, d.n1, d.tracked, d.at0, d.at1, d.tv0, d.tv1, d.ids_tmp, d.cell_pt, n_cells,
+                      d.new_aff0, d.new_aff1, d.new_valid, d.map_aff0, d.map_aff1, d.ids0, d.ids1, d.counts,
+                      d.last_id, d.capacity, d.out0, d.out1, d.overflow, d.cams, d.und0, d.und1, d.gate);
+    __syncthreads();
+    const int m0 = d.counts[0], m1 = d.counts[1];
+    if (threadIdx.x == 0) {
+        d.rb_head[0] = m0;
+        d.rb_head[1] = m1;
+        d.rb_head[2] = *d.overflow;
+        d.rb_head[3] = 0;
+    }
+    if (threadIdx.x < 4) d.rb_head[4 + threadIdx.x] = d.gate.mode != RSVIO_GATE_OFF ? d.gate.counters[threadIdx.x] : 0;
     const int k0 = min(m0, d.bnd[0]), k1 = min(m1, d.bnd[1]);
     for (int j = threadIdx.x; j < k0 + k1; j += blockDim.x) {
         const int c = j < k0 ? 0 : 1;
@@ -191,6 +219,7 @@ struct TrackerBatch {
         BatchSlot* bs = hp<BatchSlot>(off_slot);
         int32_t* st = hp<int32_t>(off_start);
         int nb = 0, k_host = 0;
+        bool any_gate = false;
         st[0] = 0;
         for (int i = 0; i < n; ++i) {
             Tracker& t = *T[i];
@@ -248,6 +277,8 @@ struct TrackerBatch {
                 s.bnd[c] = (int)bnd[2 * i + c];
             }
             s.cams = t.cams;
+            s.gate = t.gate_dev(t.wslot);
+            any_gate = any_gate || t.gated();
         }
         const int total = st[nb];
         // ONE upload, three launches, ONE read-back, ONE wait
@@ -271,8 +302,8 @@ struct TrackerBatch {
             L.tmask = dp<const int4*>(off_mask);
             enqueue_track(L, stream);
         }
-        hipLaunchKernelGGL(append_pack_batch_kernel, dim3(n), dim3(1024), 0, stream, t0.G, t0.n_cells,
-                           dp<BatchSlot>(off_slot));
+        hipLaunchKernelGGL(any_gate ? append_pack_batch_gate_kernel : append_pack_batch_kernel, dim3(n), dim3(1024),
+                           0, stream, t0.G, t0.n_cells, dp<BatchSlot>(off_slot));
         RSVIO_HIP(hipGetLastError());
         if (device_ms) RSVIO_HIP(hipEventRecord(ev[1], stream));
         RSVIO_HIP(hipMemcpyAsync(h_rb.p, d_rb.p, rb, hipMemcpyDeviceToHost, stream));
@@ -295,6 +326,7 @@ struct TrackerBatch {
             t.rslot = slot;
             t.host_count[0] = head[0];
             t.host_count[1] = head[1];
+            t.set_report(head + 4);
             const size_t ml = std::min((size_t)std::max(head[0], 0), bnd[2 * i]);
             const size_t mr = std::min((size_t)std::max(head[1], 0), bnd[2 * i + 1]);
             t.coll_n[0] = (int)ml;

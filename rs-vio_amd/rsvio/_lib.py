@@ -113,6 +113,21 @@ class StereoFrame(C.Structure):
                 ("n_l", C.c_size_t), ("n_r", C.c_size_t), ("on_device", C.c_int32), ("status", C.c_int32)]
 
 
+class StereoGate(C.Structure):
+    """rsvio_stereo_gate (144 B): the epipolar gate of a tracker handle."""
+    _fields_ = [("mode", C.c_int32), ("reserved", C.c_int32), ("max_error", C.c_double),
+                ("T_Cl_Cr", C.c_double * 16)]
+
+
+class GateCounts(C.Structure):
+    """rsvio_gate_counts (16 B): a frame's pairs before the gate, the rejected and the invalid among them."""
+    _fields_ = [("n_pairs", C.c_int32), ("n_rejected", C.c_int32), ("n_invalid", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+GATE_MODES = {"off": 0, "drop_right": 1, "drop_both": 2}
+
+
 class BaParams(C.Structure):
     _fields_ = [("max_keyframes", C.c_int32), ("max_landmarks", C.c_int32),
                 ("max_observations", C.c_int32), ("device", C.c_int32)]
@@ -223,6 +238,14 @@ SIG = {
     "rsvio_tracker_batch_destroy": (None, [P]),
     "rsvio_tracker_device_lists": (C.c_int, [P, C.POINTER(P), C.POINTER(C.c_size_t), C.POINTER(P),
                                              C.POINTER(C.c_size_t), C.POINTER(P), C.POINTER(P)]),
+    "rsvio_tracker_set_stereo_gate": (C.c_int, [P, C.POINTER(StereoGate)]),
+    "rsvio_tracker_gate_report": (C.c_int, [P, C.POINTER(GateCounts), P, P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "rsvio_stereo_gate_lists": (C.c_int, [C.POINTER(StereoGate), C.c_int32, C.c_int32, P, P, C.c_size_t, P, P,
+                                          C.c_size_t, P, P, P, C.POINTER(GateCounts)]),
+    # diagnostic (not in the header): the frame end's whole gate on two given maps, in place
+    "rsvio_dbg_stereo_gate_frame": (C.c_int, [C.POINTER(StereoGate), C.c_int32, C.c_int32, P, P, P,
+                                              C.POINTER(C.c_size_t), P, P, P, C.POINTER(C.c_size_t), P, P,
+                                              C.POINTER(GateCounts)]),
     "rsvio_pyramid_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "rsvio_build_pyramid": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, P]),
     "rsvio_track_points": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, C.c_float,

@@ -42,6 +42,16 @@ class FrameResult:
     pnp_cost: float | None = None       # its final cost
     ba_iterations: int | None = None    # LM iterations of the window's solve (the retry's, after a fallback)
     pose_covariance: np.ndarray | None = None   # Estimator(pose_covariance=True): 6x6 of T_W_B when pnp_status > 0
+    n_gate_rejected: int | None = None   # Estimator(stereo_gate=...): pairs the tracker's gate dropped; None: off
+
+
+@dataclass
+class StereoGateConfig:
+    """Estimator(stereo_gate=...): the tracker's epipolar gate (rsvio.tracker.StereoGate) with the
+    rig's own extrinsics.  mode: GATE_DROP_RIGHT / GATE_DROP_BOTH (1 / 2, or "drop_right" /
+    "drop_both"); max_error: the bound on |d_l . (E d_r)| of unit bearings (about pixels / focal)."""
+    mode: int | str
+    max_error: float
 
 
 class DeviceBackend:
@@ -119,6 +129,14 @@ class DeviceBackend:
         """StereoPatchTracker::remove_id: the ids leave the tracker before its next frame."""
         self.tracker.remove_id(np.asarray(ids, np.uint64))
 
+    def set_stereo_gate(self, gate):
+        """The tracker's epipolar gate (rsvio.tracker.StereoGate; None: off), from the next frame on."""
+        self.tracker.set_stereo_gate(gate)
+
+    def gate_counts(self):
+        """The collected frame's gate counters (they came back with its lists)."""
+        return self.tracker.gate_counts()
+
     def close(self):
         for o in (self.tracker, self.motion, self.solver, self._ba_stream):
             o.close()
@@ -133,7 +151,8 @@ class Estimator:
                  max_iterations: int = 20, thresh: float = 0.01, window: int = 10,
                  translation_threshold: float = 0.05, rotation_threshold: float = 0.05, device: int = 0,
                  backend=None, pipelined: bool = False, landmark_init: str = "ray", gate=None, cull: bool = False,
-                 robust_motion=None, drop_outliers: bool = False, pose_covariance: bool = False):
+                 robust_motion=None, drop_outliers: bool = False, pose_covariance: bool = False,
+                 stereo_gate: StereoGateConfig | None = None):
         # robust_motion: a rsvio.motion.RansacConfig -- the frame's pose and keyframe flag come from
         # MotionTracker.track_motion_tracker_robust (a stereo 3-point RANSAC, the LM on its
         # consensus set) instead of the plain LM over every joined observation; None: the
@@ -154,12 +173,23 @@ class Estimator:
         self.last_dropped = np.zeros(0, np.uint64)   # the ids it removed from the tracker
         self.backend = backend or DeviceBackend(width, height, cameras, levels, grid_size, max_iterations, thresh,
                                                 window, translation_threshold, rotation_threshold, device)
+        if stereo_gate is not None and not hasattr(self.backend, "set_stereo_gate"):
+            raise ValueError("stereo_gate needs a backend with set_stereo_gate (the device tracker)")
         # landmark_init / gate / cull: the window's (SlidingWindow): new landmarks triangulated on the
         # device instead of the depth-2.0 ray, gated landmarks left out of the map
         self.window = SlidingWindow(window, device, solver=self.backend.solver, landmark_init=landmark_init,
                                     gate=gate, cull=cull)
         self.T_B_Cl = np.asarray(T_B_Cl, np.float64)
         self.T_B_Cr = np.asarray(T_B_Cr, np.float64)
+        # stereo_gate: the tracker drops, at the end of every frame and on the device, the pairs whose
+        # two pixels are not views of one point by the rig's epipolar geometry (T_Cl_Cr = T_B_Cl^-1
+        # T_B_Cr); the gate is state of the tracker, so every consumer of its lists sees gated ones.
+        # FrameResult.n_gate_rejected counts them; None: the reference's tracker
+        self.stereo_gate = stereo_gate
+        if stereo_gate is not None:
+            from .tracker import StereoGate
+            self.backend.set_stereo_gate(StereoGate(stereo_gate.mode, stereo_gate.max_error,
+                                                    np.linalg.inv(self.T_B_Cl) @ self.T_B_Cr))
         self.frame_id = 0
         self._map_key = None
         self._tcb_key = None
@@ -191,7 +221,11 @@ class Estimator:
         return self._tcb
 
     def process_frame(self, left: np.ndarray, right: np.ndarray) -> FrameResult:
-        return self._process_tracked(self.backend.track(left, right))
+        return self._process_tracked(self._tracked(self.backend.track(left, right)))
+
+    def _tracked(self, feats):
+        """A collected frame's features with its gate count, taken before the next frame is submitted."""
+        return feats, (None if self.stereo_gate is None else int(self.backend.gate_counts().n_rejected))
 
     def run(self, frames):
         """process_frame over an iterable of (left, right) image pairs, yielding one FrameResult
@@ -211,7 +245,7 @@ class Estimator:
         in_flight = True
         try:
             while in_flight:
-                feats = self.backend.collect()
+                feats = self._tracked(self.backend.collect())
                 in_flight = False
                 nxt = next(it, None)
                 if nxt is not None:
@@ -225,7 +259,7 @@ class Estimator:
     def _process_tracked(self, feats) -> FrameResult:
         """Steps 2-3 of process_frame (estimator.rs:195-248) for a frame whose features are in."""
         self.frame_id += 1
-        (ids_l, uv_l), (ids_r, uv_r) = feats
+        ((ids_l, uv_l), (ids_r, uv_r)), n_gate_rejected = feats
         frame = Frame(frame_id=self.frame_id, T_W_B=np.eye(4), T_B_Cl=self.T_B_Cl, T_B_Cr=self.T_B_Cr,
                       is_keyframe=True, left_features=(ids_l, uv_l), right_features=(ids_r, uv_r))
         pnp_status = pnp_iters = pnp_cost = pose_cov = None
@@ -272,7 +306,7 @@ class Estimator:
                     ba_iters = None if r is None else int(r.iterations)
         out = FrameResult(self.frame_id, frame.is_keyframe, frame.T_W_B.copy(), len(ids_l), len(ids_r),
                           pnp_status, ba_status, pnp_iterations=pnp_iters, pnp_cost=pnp_cost,
-                          ba_iterations=ba_iters, pose_covariance=pose_cov)
+                          ba_iterations=ba_iters, pose_covariance=pose_cov, n_gate_rejected=n_gate_rejected)
         if pending:
             self._pending_frame = (out, frame)
         return out

@@ -9,6 +9,7 @@ functions mirror the reference's module-level ``build_image_pyramid`` (:209-220)
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -64,6 +65,55 @@ def detect_key_points(img: np.ndarray, grid_size: int, existing_xy: np.ndarray |
 
 
 FEATURE_DTYPE = np.dtype([("id", np.uint64), ("x", np.float32), ("y", np.float32), ("r", np.float32, 4)])
+
+GATE_OFF, GATE_DROP_RIGHT, GATE_DROP_BOTH = 0, 1, 2
+
+
+@dataclass
+class StereoGate:
+    """rsvio_stereo_gate: the epipolar gate of a tracker handle.  mode: GATE_DROP_RIGHT / GATE_DROP_BOTH
+    (or "drop_right" / "drop_both"); max_error: the bound on e = |d_l . (E d_r)| of unit bearings;
+    T_Cl_Cr: 4 x 4, the right camera's pose in the left camera's frame (x_l = R x_r + t)."""
+    mode: int | str
+    max_error: float
+    T_Cl_Cr: np.ndarray
+
+    def struct(self) -> _lib.StereoGate:
+        g = _lib.StereoGate()
+        g.mode = _lib.GATE_MODES[self.mode] if isinstance(self.mode, str) else int(self.mode)
+        g.max_error = float(self.max_error)
+        T = np.asarray(self.T_Cl_Cr, np.float64)
+        if T.shape != (4, 4):
+            raise ValueError("T_Cl_Cr must be 4 x 4")
+        g.T_Cl_Cr[:] = T.reshape(16).tolist()
+        return g
+
+
+@dataclass
+class GateCounts:
+    n_pairs: int = 0      # ids in both cameras' maps before the gate
+    n_rejected: int = 0   # of them, the ones the gate dropped
+    n_invalid: int = 0    # of those, the ones without a bearing (a failed unprojection, RAY with s < 0)
+
+
+def stereo_gate_lists(gate: StereoGate, convention_l, convention_r, ids_l, uv_l, ids_r, uv_r):
+    """rsvio_stereo_gate_lists: the gate's device function on two lists with ascending ids (uv: the
+    stored f32 unprojected coordinates); (keep_l, keep_r, err_r, GateCounts) with bool keeps and
+    err_r NaN for an unpaired or invalid right entry."""
+    from .camera import CONVENTIONS
+    cl, cr = (CONVENTIONS[c] if isinstance(c, str) else int(c) for c in (convention_l, convention_r))
+    ids_l, ids_r = np.ascontiguousarray(ids_l, np.uint64), np.ascontiguousarray(ids_r, np.uint64)
+    uv_l = np.ascontiguousarray(uv_l, np.float32).reshape(-1, 2)
+    uv_r = np.ascontiguousarray(uv_r, np.float32).reshape(-1, 2)
+    if len(uv_l) != len(ids_l) or len(uv_r) != len(ids_r):
+        raise ValueError("one coordinate pair per id")
+    keep_l, keep_r = np.zeros(len(ids_l), np.uint8), np.zeros(len(ids_r), np.uint8)
+    err_r = np.zeros(len(ids_r), np.float64)
+    g, c = gate.struct(), _lib.GateCounts()
+    check(_lib.load().rsvio_stereo_gate_lists(C.byref(g), cl, cr, ptr(ids_l), ptr(uv_l), len(ids_l), ptr(ids_r),
+                                              ptr(uv_r), len(ids_r), ptr(keep_l), ptr(keep_r), ptr(err_r),
+                                              C.byref(c)))
+    return keep_l.astype(bool), keep_r.astype(bool), err_r, GateCounts(c.n_pairs, c.n_rejected, c.n_invalid)
 
 
 class StereoPatchTracker:
@@ -170,6 +220,33 @@ class StereoPatchTracker:
         ur = np.zeros((self._n[1], 2), np.float32)
         check(_lib.load().rsvio_tracker_undistorted(self._h, ptr(ul), self._n[0], ptr(ur), self._n[1]))
         return ul, ur
+
+    def set_stereo_gate(self, gate: StereoGate | None):
+        """rsvio_tracker_set_stereo_gate: from the next frame on, every pair (an id in both cameras'
+        maps) whose epipolar error exceeds gate.max_error, or that has no bearing, leaves cam1's map
+        (GATE_DROP_RIGHT) or both maps (GATE_DROP_BOTH) at the end of the frame, on the device.  Needs
+        set_cameras; None turns it off."""
+        if gate is None:
+            check(_lib.load().rsvio_tracker_set_stereo_gate(self._h, None))
+            return
+        g = gate.struct()
+        check(_lib.load().rsvio_tracker_set_stereo_gate(self._h, C.byref(g)))
+
+    def gate_counts(self) -> GateCounts:
+        """The last collected frame's gate counters alone (they came back with its lists: no device call)."""
+        c, n = _lib.GateCounts(), C.c_size_t(0)
+        check(_lib.load().rsvio_tracker_gate_report(self._h, C.byref(c), None, None, 0, C.byref(n)))
+        return GateCounts(c.n_pairs, c.n_rejected, c.n_invalid)
+
+    def gate_report(self):
+        """rsvio_tracker_gate_report of the last collected frame: (GateCounts, the rejected ids
+        ascending, their errors -- NaN for a pair without a bearing); zeros and empty with the gate off."""
+        c = self.gate_counts()
+        ids, err = np.zeros(c.n_rejected, np.uint64), np.zeros(c.n_rejected, np.float64)
+        n = C.c_size_t(0)
+        if c.n_rejected:
+            check(_lib.load().rsvio_tracker_gate_report(self._h, None, ptr(ids), ptr(err), len(ids), C.byref(n)))
+        return c, ids, err
 
     def remove_id(self, ids):
         """StereoPatchTracker::remove_id (feature_tracker.rs:201-206): the device lists are

@@ -85,6 +85,8 @@ GROUPS = {
     "rsvio_pnp_set_stream": "motion tracking (continued)",
     "rsvio_tracker_batch_create": "batched tracker: one stereo frame per handle, many handles per call; the last "
                                   "frame's lists on the device",
+    "rsvio_tracker_set_stereo_gate": "stereo gate: the epipolar check on every frame's pairs (state of a handle), "
+                                     "its report, and the same check on two given lists",
 }
 
 
