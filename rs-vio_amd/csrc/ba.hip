@@ -37,6 +37,7 @@
 //   ba_k5_x2.hpp        K5 on the VALU, two rows per lane (11..20 free keyframes)
 //   ba_landmarks.hpp    triangulation and the depth / reprojection gate
 //   ba_covariance.hpp   pose and landmark covariance
+//   ba_batch.hpp        host: BundleBatch, the batched mode over B window handles
 // and, standing alone, ba_dispatch.hpp (host: n_free -> the K5 templates' NF).  The other stages
 // are still here, in the order of the map above, and are to move out one stage per change, each
 // shown to leave the device code alone by tools/isa_compare.py.
@@ -3238,6 +3239,33 @@ __attribute__((target("popcnt"))) static inline int slot_count(unsigned long lon
     return __builtin_popcountll((m | (m >> 1)) & kEvenBits);
 }
 
+// The descriptor kernels' launches (K4, K4c, K6) over B rows of a table: a handle's own graph (B = 1,
+// wcap waves) and the batch's chains.  Callers check hipGetLastError, and launch their own K5 and decision.
+struct DescChain {
+    hipStream_t stream;
+    const WinDesc* D;
+    int B, waves, chunks;  // rows; K4 / K6 and K4c workgroups per row
+    void linearize(double lambda0) const {
+        hipLaunchKernelGGL(bab_linearize, dim3(waves, B), dim3(64), 0, stream, D, lambda0);
+    }
+    void schur(int wi, const LmArgs& la) const {
+        hipLaunchKernelGGL(bab_schur_chunks, dim3(chunks, B), dim3(kSchurThreads), 0, stream, D, wi, la);
+    }
+    // hout: the last K6 of a chunk with the state export on (k6_body's LAST form, the single graph's)
+    void backsub(int wi, double* hout = nullptr) const {
+        if (hout)
+            hipLaunchKernelGGL(bab_backsub_trial_export, dim3(waves, B), dim3(64), 0, stream, D, wi, hout);
+        else
+            hipLaunchKernelGGL(bab_backsub_relinearize, dim3(waves, B), dim3(64), 0, stream, D, wi);
+    }
+};
+
+// f(std::true_type) for a triangulation, f(std::false_type) for a check: the landmark kernels' TRI
+template <class F>
+static void with_tri(bool tri, F&& f) {
+    tri ? f(std::true_type{}) : f(std::false_type{});
+}
+
 struct BundleAdjuster {
     rsvio_ba_params P{};
     hipStream_t stream = nullptr;
@@ -3350,11 +3378,12 @@ struct BundleAdjuster {
     int p2p_share = 1;            // ranks on this rank's device (attach_p2p)
     bool p2p_fold4() const { return fold_lvl == 4 && p2p_fold(); }
     const WinDesc* dptr() const { return reinterpret_cast<const WinDesc*>(d_arena.p + lay.desc); }
-    void fill_desc(WinDesc& d) const {
+    // the window's row of a descriptor table (its own D[0], or a row of the batch's) at an LM configuration
+    void fill_desc(WinDesc& d, double huber_delta, int chol) const {
         d = WinDesc{};
         d.G = G;
-        d.G.huber_delta = desc_huber;
-        d.G.chol = desc_chol;
+        d.G.huber_delta = huber_delta;
+        d.G.chol = chol;
         d.Pr = prob();
         d.W[0] = work(0);
         d.W[1] = work(1);
@@ -3372,8 +3401,7 @@ struct BundleAdjuster {
         desc_pending = false;
         desc_huber = G.huber_delta;
         desc_chol = G.chol;
-        hdesc.G.huber_delta = desc_huber;
-        hdesc.G.chol = desc_chol;
+        fill_desc(hdesc, desc_huber, desc_chol);
         if (!h_desc1.p) h_desc1.alloc(1);
         *h_desc1.p = hdesc;
         settled = false;
@@ -3959,7 +3987,7 @@ struct BundleAdjuster {
         for (int c = 0; c < 2; ++c)
             for (int i = 0; i < 16; ++i) G.TCB[c].m[i] = TCB2[16 * c + i];
         grow_buffers();  // (before the descriptor: it holds their addresses)
-        fill_desc(hdesc);
+        fill_desc(hdesc, desc_huber, desc_chol);
         std::memcpy(hb + L.desc, &hdesc, sizeof(WinDesc));
         mark();
         if (stage_kernel) {
@@ -4214,13 +4242,15 @@ struct BundleAdjuster {
 
     // descriptor mode (start_graph): K4, the LM iterations and K7 from the device descriptor, K4 / K6 on
     // wcap >= n_wave workgroups -- the same kernels' bodies as enqueue_start / _iteration / _decide
+    DescChain chain_d(int wcap) const { return DescChain{stream, dptr(), 1, wcap, G.n_chunk}; }
     void enqueue_start_d(double lambda0, int wcap) {
-        hipLaunchKernelGGL(bab_linearize, dim3(wcap, 1), dim3(64), 0, stream, dptr(), lambda0);
+        chain_d(wcap).linearize(lambda0);
         RSVIO_HIP(hipGetLastError());
     }
     void enqueue_iteration_d(const rsvio_lm_cfg& cfg, int it, int wcap, bool last = false) {
         const int wi = it & 1;  // work(it) depends on the parity of it only
-        hipLaunchKernelGGL(bab_schur_chunks, dim3(G.n_chunk, 1), dim3(kSchurThreads), 0, stream, dptr(), wi, lm_args(cfg));
+        const DescChain ch = chain_d(wcap);
+        ch.schur(wi, lm_args(cfg));
         RSVIO_HIP(hipGetLastError());
         const bool k5 = dispatch_panel_nf(G.n_free, [&](auto nf) {
             constexpr int NF = decltype(nf)::value;
@@ -4228,10 +4258,7 @@ struct BundleAdjuster {
         });
         if (!k5) throw std::logic_error("descriptor mode: more than 10 free keyframes");
         RSVIO_HIP(hipGetLastError());
-        if (last && lean_last())
-            hipLaunchKernelGGL(bab_backsub_trial_export, dim3(wcap, 1), dim3(64), 0, stream, dptr(), wi, h_out.p);
-        else
-            hipLaunchKernelGGL(bab_backsub_relinearize, dim3(wcap, 1), dim3(64), 0, stream, dptr(), wi);
+        ch.backsub(wi, last && lean_last() ? h_out.p : nullptr);
         RSVIO_HIP(hipGetLastError());
     }
     void enqueue_decide_d(const rsvio_lm_cfg& cfg, int it) {
@@ -4246,6 +4273,17 @@ struct BundleAdjuster {
     // chunk; the first chunk is the previous solve's iteration count (consecutive windows
     // converge alike), so the common case costs one read-back and no iteration enqueued after
     // convergence.
+    // sliding_window.rs:303-319: too few residuals / underconstrained -> skipped (Ok(false))
+    bool underconstrained() const { return G.n_obs < 6 || G.n_obs < G.n_kf + G.n_lm; }
+    // the first chunk of a solve: the previous solve's iteration count
+    static int first_chunk(int last_iterations, int max_it) { return std::min(std::max(last_iterations, 1), max_it); }
+    static void fill_result(rsvio_ba_result& res, const LmState& s, float ms) {
+        res.status = s.status;
+        res.iterations = s.iter;
+        res.initial_cost = s.initial_cost;
+        res.final_cost = s.cost;
+        res.solve_ms = ms;
+    }
     struct Pending {
         bool active = false, skipped = false;
         bool by_tick = false;  // the wait mode fixed at start(): finish() never switches it mid-solve
@@ -4305,8 +4343,7 @@ struct BundleAdjuster {
         pend.by_tick = by_tick();
         state_export = false;
         at_initial = false;
-        // sliding_window.rs:303-319: too few residuals / underconstrained -> skipped (Ok(false))
-        if (!sharded() && (G.n_obs < 6 || G.n_obs < G.n_kf + G.n_lm)) {
+        if (!sharded() && underconstrained()) {
             pend.skipped = true;
             return;
         }
@@ -4314,7 +4351,7 @@ struct BundleAdjuster {
         settled = false;
         state_fresh = false;  // K4 (K0 folded in) sets both state buffers
         if (!pend.by_tick) RSVIO_HIP(hipEventRecord(ev0, stream));  // the ticket carries device stamps
-        int k = std::min(std::max(last_iterations, 1), pend.max_it);
+        int k = first_chunk(last_iterations, pend.max_it);
         // a new problem (every keyframe in the Estimator) is re-captured: capture + instantiate +
         // one launch measured cheaper in host time than its ~25 direct launches (config-4 BA stage
         // 0.100 vs 0.115 ms per frame, round 2), so graphs stay on for fresh problems too
@@ -4380,12 +4417,7 @@ struct BundleAdjuster {
             settled = true;
             RSVIO_HIP(hipEventElapsedTime(&ms, ev0, ev1));
         }
-        const LmState& s = *h_state.p;
-        res->status = s.status;
-        res->iterations = s.iter;
-        res->initial_cost = s.initial_cost;
-        res->final_cost = s.cost;
-        res->solve_ms = ms;
+        fill_result(*res, *h_state.p, ms);
     }
 
     // ---- peer-to-peer collective (sharded path) ----
@@ -4648,6 +4680,48 @@ struct BundleAdjuster {
         RSVIO_HIP(hipStreamSynchronize(stream));
     }
 
+    // the refusals of a landmark call, single and batched (what: the caller's prefix; slot: the
+    // batch's slot, named at the end of the text) -- the texts are built only when throwing
+    void lm_check(const char* what, int n_lm, int slot = -1) const {
+        if (!pend.active && has_problem && n_lm == G.n_lm) return;
+        const std::string w = what, s = slot < 0 ? "" : " (slot " + std::to_string(slot) + ")";
+        if (pend.active) throw CallOrderError(w + ": a solve is in flight (call rsvio_ba_wait first)" + s);
+        if (!has_problem) throw std::invalid_argument(w + ": no problem uploaded" + s);
+        throw std::invalid_argument(w + ": n_lm differs from the uploaded problem's" + s);
+    }
+    // What a landmark kernel of this window runs on (arguments checked by lm_check; a check's
+    // caller has made h_state current; nothing is enqueued): the selection staged under ev_sel,
+    // the state -- the initial one for tri, else what get_state would return -- the gate, the outputs.
+    LmDesc lm_plan(bool tri, const uint8_t* sel, const rsvio_landmark_gate& g) {
+        LmDesc d{};
+        if (tri && sel) {
+            if (sel_pending) RSVIO_HIP(hipEventSynchronize(ev_sel));  // the previous call's kernel has read the staging
+            sel_pending = false;
+            std::memcpy(h_lm_sel.p, sel, (size_t)G.n_lm);
+            d.sel = h_lm_sel_dev;
+        }
+        // (tri: a get_state since set_problem copied the initial state into the state buffers)
+        if (tri && at_initial) state_fresh = true;
+        const Work wk = work_at(0);
+        const bool initial = tri || state_fresh;
+        d.pose = initial ? wk.pose_init : wk.pose[h_state.p->cur];
+        d.pw = initial ? wk.pw_init : wk.pw[h_state.p->cur];
+        d.gate = LmGate{tri ? g.mode : (int)RSVIO_TRI_ALL_VIEWS, g.min_depth, g.max_depth, g.max_sq_error};
+        d.G = G;
+        d.Pr = prob();
+        d.obs_mask = obs_mask_dev();
+        d.pw_out = reinterpret_cast<double*>(d_arena.p + lay.pw_init);
+        d.info = d_lm_info.p;
+        return d;
+    }
+    // the report in h_lm_info (copied and waited for by the caller) handed out, and its OK count
+    void lm_deliver(rsvio_landmark_info* info_out, int32_t* n_ok) const {
+        if (info_out) std::memcpy(info_out, h_lm_info.p, sizeof(rsvio_landmark_info) * (size_t)G.n_lm);
+        if (!n_ok) return;
+        int32_t c = 0;
+        for (int l = 0; l < G.n_lm; ++l) c += (h_lm_info.p[l].flags & RSVIO_LM_OK) ? 1 : 0;
+        *n_ok = c;
+    }
     // Triangulation (tri) or the gate's report on the current state (check), enqueued on the
     // handle's stream.  tri reads the INITIAL poses and the observations -- never the points, so
     // it is idempotent -- and writes the accepted points of the selected landmarks into the arena's
@@ -4658,62 +4732,30 @@ struct BundleAdjuster {
     // check reads what get_state would return and writes nothing but the report.
     void landmarks(bool tri, const uint8_t* sel, int n_lm, const rsvio_landmark_gate& g, double* pw_out,
                    rsvio_landmark_info* info_out, int32_t* n_ok) {
-        const char* what = tri ? "triangulate" : "check_landmarks";
-        if (pend.active) throw CallOrderError(std::string(what) + ": a solve is in flight (call rsvio_ba_wait first)");
-        if (!has_problem) throw std::invalid_argument(std::string(what) + ": no problem uploaded");
-        if (n_lm != G.n_lm) throw std::invalid_argument(std::string(what) + ": n_lm differs from the uploaded problem's");
+        lm_check(tri ? "triangulate" : "check_landmarks", n_lm);
         if (n_ok) *n_ok = 0;
         if (!n_lm) return;
-        const unsigned char* d_sel = nullptr;
-        if (tri && sel) {
-            if (sel_pending) RSVIO_HIP(hipEventSynchronize(ev_sel));  // the previous call's kernel has read the staging
-            sel_pending = false;
-            std::memcpy(h_lm_sel.p, sel, (size_t)n_lm);
-            d_sel = h_lm_sel_dev;
-        }
-        const Work wk = work_at(0);
-        const double *pose = wk.pose_init, *pw = wk.pw_init;
-        if (tri) {
-            // (a get_state since set_problem copied the initial state into the state buffers)
-            if (at_initial) state_fresh = true;
-        } else {
-            settle();
-            if (!state_fresh) {
-                const int cur = h_state.p->cur;
-                pose = wk.pose[cur];
-                pw = wk.pw[cur];
-            }
-        }
-        const LmGate gate{tri ? g.mode : (int)RSVIO_TRI_ALL_VIEWS, g.min_depth, g.max_depth, g.max_sq_error};
-        const auto* obs_mask = reinterpret_cast<const unsigned long long*>(d_arena.p + lay.mask);
-        double* pw_init = reinterpret_cast<double*>(d_arena.p + lay.pw_init);
-        const dim3 grid(G.n_wave + (n_lm + 63) / 64), block(64);
+        if (!tri) settle();  // h_state is the last decision's
+        const LmDesc d = lm_plan(tri, sel, g);
         settled = false;
-        if (tri)
-            hipLaunchKernelGGL(ba_landmarks<true>, grid, block, 0, stream, G, prob(), obs_mask, pose, pw, pw_init, d_sel,
-                               gate, d_lm_info.p);
-        else
-            hipLaunchKernelGGL(ba_landmarks<false>, grid, block, 0, stream, G, prob(), obs_mask, pose, pw, pw_init,
-                               d_sel, gate, d_lm_info.p);
+        with_tri(tri, [&](auto t) {
+            hipLaunchKernelGGL(ba_landmarks<decltype(t)::value>, dim3(G.n_wave + (n_lm + 63) / 64), dim3(64), 0, stream,
+                               d.G, d.Pr, d.obs_mask, d.pose, d.pw, d.pw_out, d.sel, d.gate, d.info);
+        });
         RSVIO_HIP(hipGetLastError());
-        if (d_sel) {
+        if (d.sel) {
             RSVIO_HIP(hipEventRecord(ev_sel, stream));
             sel_pending = true;
         }
         if (!pw_out && !info_out && !n_ok) return;
         if (pw_out)
-            RSVIO_HIP(hipMemcpyAsync(pw_out, pw_init, sizeof(double) * 3 * (size_t)n_lm, hipMemcpyDeviceToHost, stream));
+            RSVIO_HIP(hipMemcpyAsync(pw_out, d.pw_out, sizeof(double) * 3 * (size_t)n_lm, hipMemcpyDeviceToHost, stream));
         if (info_out || n_ok)
             RSVIO_HIP(hipMemcpyAsync(h_lm_info.p, d_lm_info.p, sizeof(rsvio_landmark_info) * (size_t)n_lm,
                                      hipMemcpyDeviceToHost, stream));
         settle();
         sel_pending = false;
-        if (info_out) std::memcpy(info_out, h_lm_info.p, sizeof(rsvio_landmark_info) * (size_t)n_lm);
-        if (n_ok) {
-            int32_t c = 0;
-            for (int l = 0; l < n_lm; ++l) c += (h_lm_info.p[l].flags & RSVIO_LM_OK) ? 1 : 0;
-            *n_ok = c;
-        }
+        lm_deliver(info_out, n_ok);
     }
 
     // the argument checks of covariance, single and batched (what: the caller's prefix)
@@ -4947,461 +4989,8 @@ struct BundleAdjuster {
     }
 };
 
-// Batched mode over B window handles (their problems uploaded by rsvio_ba_set_problem): one
-// launch chain on the batch's stream, the host reading the B LM states once per chunk.
-struct BundleBatch {
-    std::vector<BundleAdjuster*> win;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    DevBuf<WinDesc> d_desc;
-    HostBuf<WinDesc> h_desc;
-    HostBuf<LmState> h_states;
-    DevBuf<int> d_dmap;
-    HostBuf<int> h_dmap;
-    std::vector<hipEvent_t> ev_win;  // per window: its stream's pending work (an upload) before the batch
-    int last_iterations = 3;
-    // the batched keyframe step (triangulate, check, covariance): the landmark kernels' table has
-    // its own pinned image and an event for its upload, because an enqueue-only triangulate
-    // returns before the copy has read it; the covariance's status words and costs sit in one
-    // array of the batch (one read-back for all windows), its other scratch is each handle's
-    DevBuf<LmDesc> d_lmdesc;
-    HostBuf<LmDesc> h_lmdesc;
-    hipEvent_t ev_lmcopy = nullptr, ev_after = nullptr;
-    bool lmcopy_pending = false;
-    DevBuf<CovDesc> d_covdesc;
-    HostBuf<CovDesc> h_covdesc;
-    DevBuf<int> d_cst;
-    HostBuf<int> h_cst;
-    DevBuf<double> d_cost;
-    HostBuf<double> h_cost;
-
-    void init(BundleAdjuster* const* w, int n) {
-        if (n < 1) throw std::invalid_argument("a batch needs at least one window");
-        for (int i = 0; i < n; ++i) {
-            if (!w[i]) throw std::invalid_argument("null window handle");
-            if (i && w[i]->P.device != w[0]->P.device) throw std::invalid_argument("windows on different devices");
-            if (w[i]->sharded()) throw std::invalid_argument("a sharded window cannot join a batch");
-            for (int j = 0; j < i; ++j)  // two grid rows on one set of state buffers would race
-                if (w[j] == w[i]) throw std::invalid_argument("a window handle appears twice in the batch");
-            win.push_back(w[i]);
-        }
-        device = w[0]->P.device;
-        RSVIO_HIP(hipSetDevice(device));
-        RSVIO_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        RSVIO_HIP(hipEventCreate(&ev0));
-        RSVIO_HIP(hipEventCreate(&ev1));
-        ev_win.assign(n, nullptr);
-        for (int i = 0; i < n; ++i) RSVIO_HIP(hipEventCreateWithFlags(&ev_win[i], hipEventDisableTiming));
-        d_desc.alloc(n);
-        h_desc.alloc(n);
-        h_states.alloc(n, hipHostMallocCoherent);
-        RSVIO_HIP(hipEventCreateWithFlags(&ev_lmcopy, hipEventDisableTiming));
-        RSVIO_HIP(hipEventCreateWithFlags(&ev_after, hipEventDisableTiming));
-        d_lmdesc.alloc(n);
-        h_lmdesc.alloc(n);
-        d_covdesc.alloc(n);
-        h_covdesc.alloc(n);
-        d_cst.alloc(2 * (size_t)n);
-        h_cst.alloc(2 * (size_t)n);
-        d_cost.alloc(n);
-        h_cost.alloc(n);
-    }
-    ~BundleBatch() {
-        if (stream) (void)hipStreamSynchronize(stream);
-        if (ev_lmcopy) (void)hipEventDestroy(ev_lmcopy);
-        if (ev_after) (void)hipEventDestroy(ev_after);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        for (hipEvent_t e : ev_win)
-            if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-
-    void launch_k5(int nf, int wi) {
-        const int B = (int)win.size();
-        const bool k5 = dispatch_panel_nf(nf, [&](auto c) {
-            constexpr int NF = decltype(c)::value;
-            hipLaunchKernelGGL(bab_camera_solve<NF>, dim3(B), dim3(kK5Threads), 0, stream, d_desc.p, wi);
-        }) || dispatch_block_nf(nf, [&](auto c) {
-            constexpr int NF = decltype(c)::value;
-            hipLaunchKernelGGL(bab_camera_solve_blk<NF>, dim3(B), dim3(64 * kBkWaves), 0, stream, d_desc.p, wi);
-        });
-        if (!k5) throw std::logic_error("batched mode: no camera-solve template for this window size");
-        RSVIO_HIP(hipGetLastError());
-    }
-
-    // on: one byte per window (null = every window).  A window that is off is a skipped row of the
-    // descriptor table: it is not read, written or required to hold a problem, and res[i] is left.
-    void run(const rsvio_lm_cfg& cfg, rsvio_ba_result* res, const uint8_t* on = nullptr) {
-        const int B = (int)win.size();
-        int nf = 1, max_wave = 1, max_chunk = 1, active = 0;
-        std::vector<int> skip(B, 0);
-        size_t ne_total = 0;
-        for (int i = 0; i < B; ++i) {
-            if (on && !on[i]) continue;
-            const BundleAdjuster& w = *win[i];
-            const std::string slot = on ? " (window " + std::to_string(i) + ")" : std::string();
-            if (w.pend.active)
-                throw CallOrderError("rsvio_ba_batch_run: a solve is in flight (call rsvio_ba_wait first)" + slot);
-            if (!w.has_problem) throw std::invalid_argument("batch window without a problem" + slot);
-        }
-        for (int i = 0; i < B; ++i) {
-            if (on && !on[i]) {
-                skip[i] = 2;
-                continue;
-            }
-            BundleAdjuster& w = *win[i];
-            w.state_export = false;  // the batch's decisions leave the state in device memory
-            const Geometry& G = w.G;
-            // sliding_window.rs:303-319 guards, as the single-window start()
-            skip[i] = (G.n_obs < 6 || G.n_obs < G.n_kf + G.n_lm || G.n_wave == 0) ? 1 : 0;
-            if (skip[i]) continue;
-            ++active;
-            nf = std::max(nf, G.n_free);
-            max_wave = std::max(max_wave, G.n_wave);
-            max_chunk = std::max(max_chunk, G.n_chunk);
-            ne_total += (size_t)36 * G.n_pb + 12 * G.n_free;
-        }
-        // past 10 free keyframes every window runs the 6x6-block solver's padded template
-        if (nf > 10) nf = bk_template_nf(nf);
-        max_wave = (max_wave + kGrp - 1) / kGrp * kGrp;  // wave w on XCD w % 8 in every window
-        // descriptors and the camera-solve maps for the batch's template (b row at 6 nf)
-        if (h_dmap.n < std::max<size_t>(ne_total, 1)) {
-            h_dmap.alloc(ne_total + 1);
-            d_dmap.alloc(ne_total + 1);
-        }
-        size_t off = 0;
-        for (int i = 0; i < B; ++i) {
-            BundleAdjuster& w = *win[i];
-            WinDesc& d = h_desc.p[i];
-            if (skip[i] == 2) {  // off: no field of the handle is read
-                d = WinDesc{};
-                d.skip = 1;
-                continue;
-            }
-            d.skip = skip[i];
-            d.G = w.G;
-            d.G.huber_delta = cfg.huber_delta;
-            d.G.chol = cfg.linear_solver == RSVIO_SOLVER_CHOLESKY ? 1 : 0;
-            d.Pr = w.prob();
-            d.W[0] = w.work(0);
-            d.W[1] = w.work(1);
-            d.W[2] = w.work_at(0);
-            d.W[3] = w.work_at(1);
-            if (skip[i]) continue;
-            const size_t ne = (size_t)36 * w.G.n_pb + 12 * w.G.n_free;
-            mf_dense_map(w.G.n_free, w.G.n_pb, w.hs_pb_fa.data(), w.hs_pb_fb.data(), h_dmap.p + off, 6 * nf,
-                         nf > 10 ? kBkLd : kMfLd);
-            d.Pr.dmap = d_dmap.p + off;
-            off += ne;
-        }
-        for (int i = 0; i < B; ++i) {
-            if (skip[i] == 1) {
-                res[i] = rsvio_ba_result{};
-                res[i].status = RSVIO_LM_SKIPPED;
-            }
-        }
-        if (!active) return;
-        // the batch's kernels read what each window's stream may still be writing (set_problem's
-        // upload and ba_build_layout are asynchronous): the batch stream waits on an event of each
-        // window's stream instead of synchronising the host
-        for (int i = 0; i < B; ++i) {
-            BundleAdjuster& w = *win[i];
-            if (skip[i] == 2 || w.settled) continue;
-            RSVIO_HIP(hipEventRecord(ev_win[i], w.stream));
-            RSVIO_HIP(hipStreamWaitEvent(stream, ev_win[i], 0));
-        }
-        RSVIO_HIP(hipMemcpyAsync(d_dmap.p, h_dmap.p, sizeof(int) * std::max<size_t>(off, 1), hipMemcpyHostToDevice, stream));
-        RSVIO_HIP(hipMemcpyAsync(d_desc.p, h_desc.p, sizeof(WinDesc) * B, hipMemcpyHostToDevice, stream));
-        RSVIO_HIP(hipEventRecord(ev0, stream));
-        hipLaunchKernelGGL(bab_linearize, dim3(max_wave, B), dim3(64), 0, stream, d_desc.p, cfg.lambda_init);
-        RSVIO_HIP(hipGetLastError());
-        const LmArgs la{cfg.max_iterations, cfg.cost_tolerance, cfg.parameter_tolerance};
-        const int max_it = std::max(cfg.max_iterations, 1);
-        int enq = 0;
-        int k = std::min(std::max(last_iterations, 1), max_it);
-        int max_iter_seen = 0;
-        while (true) {
-            for (int i = 0; i < k; ++i, ++enq) {
-                const int wi = enq & 1;
-                hipLaunchKernelGGL(bab_schur_chunks, dim3(max_chunk, B), dim3(kSchurThreads), 0, stream, d_desc.p, wi, la);
-                RSVIO_HIP(hipGetLastError());
-                launch_k5(nf, wi);
-                hipLaunchKernelGGL(bab_backsub_relinearize, dim3(max_wave, B), dim3(64), 0, stream, d_desc.p, wi);
-                RSVIO_HIP(hipGetLastError());
-            }
-            hipLaunchKernelGGL(bab_lm_decide, dim3(B), dim3(64), 0, stream, d_desc.p, 2 + (enq & 1), la, h_states.p);
-            RSVIO_HIP(hipGetLastError());
-            RSVIO_HIP(hipEventRecord(ev1, stream));
-            RSVIO_HIP(hipStreamSynchronize(stream));
-            bool all_done = true;
-            for (int i = 0; i < B; ++i)
-                if (!skip[i]) {
-                    all_done = all_done && h_states.p[i].done;
-                    max_iter_seen = std::max(max_iter_seen, h_states.p[i].iter);
-                }
-            if (all_done || enq >= max_it) break;
-            k = std::min(2, max_it - enq);
-        }
-        float ms = 0.0f;
-        RSVIO_HIP(hipEventElapsedTime(&ms, ev0, ev1));
-        last_iterations = std::max(max_iter_seen, 1);
-        for (int i = 0; i < B; ++i) {
-            if (skip[i]) continue;
-            BundleAdjuster& w = *win[i];
-            const LmState& st = h_states.p[i];
-            *w.h_state.p = st;
-            w.state_fresh = false;
-            w.at_initial = false;
-            // the window's stream ran nothing after the event the batch waited on, and the batch
-            // stream is synchronised: both are idle
-            w.settled = true;
-            w.destroy_retired();
-            w.last_iterations = st.iter;
-            res[i].status = st.status;
-            res[i].iterations = st.iter;
-            res[i].initial_cost = st.initial_cost;
-            res[i].final_cost = st.cost;
-            res[i].solve_ms = ms;
-        }
-    }
-
-    // the batch stream waits, on the device, for what window i's own stream still has enqueued
-    void after_window(int i) {
-        BundleAdjuster& w = *win[i];
-        if (w.settled) return;
-        RSVIO_HIP(hipEventRecord(ev_win[i], w.stream));
-        RSVIO_HIP(hipStreamWaitEvent(stream, ev_win[i], 0));
-    }
-    // after a host wait on the batch stream: window i's stream ran nothing since after_window
-    void idle_window(int i) {
-        BundleAdjuster& w = *win[i];
-        w.settled = true;
-        w.sel_pending = false;
-        w.destroy_retired();
-    }
-
-    // rsvio_ba_batch_triangulate (tri) / _check_landmarks: BundleAdjuster::landmarks per slot, by
-    // one bab_landmarks launch.  The gates were validated by the caller (gate[i]: slot i's).
-    void landmarks(bool tri, const uint8_t* on, const std::vector<const rsvio_landmark_gate*>& gate,
-                   rsvio_ba_landmark_slot* slots, double* device_ms) {
-        const std::string what = tri ? "rsvio_ba_batch_triangulate" : "rsvio_ba_batch_check_landmarks";
-        const int B = (int)win.size();
-        int n_act = 0;
-        bool want = !tri;
-        for (int i = 0; i < B; ++i) {
-            if (on && !on[i]) continue;
-            const BundleAdjuster& w = *win[i];
-            const std::string slot = " (slot " + std::to_string(i) + ")";
-            if (w.pend.active) throw CallOrderError(what + ": a solve is in flight (call rsvio_ba_wait first)" + slot);
-            if (!w.has_problem) throw std::invalid_argument(what + ": no problem uploaded" + slot);
-            if (slots[i].n_lm != w.G.n_lm)
-                throw std::invalid_argument(what + ": n_lm differs from the uploaded problem's" + slot);
-            ++n_act;
-            want = want || (tri && slots[i].p_W_out) || slots[i].info_out;
-        }
-        if (device_ms) *device_ms = 0.0;
-        if (!n_act) return;
-        if (lmcopy_pending) RSVIO_HIP(hipEventSynchronize(ev_lmcopy));  // the last upload has read the image
-        lmcopy_pending = false;
-        int max_blocks = 0;
-        std::vector<char> live(B, 0);
-        for (int i = 0; i < B; ++i) {
-            LmDesc& d = h_lmdesc.p[i];
-            d = LmDesc{};
-            d.skip = 1;
-            if (on && !on[i]) continue;
-            BundleAdjuster& w = *win[i];
-            rsvio_ba_landmark_slot& sl = slots[i];
-            sl.n_ok = want ? 0 : -1;
-            sl.status = RSVIO_OK;
-            const int n_lm = w.G.n_lm;
-            if (!n_lm) continue;
-            live[i] = 1;
-            if (tri && sl.lm_mask) {
-                if (w.sel_pending) RSVIO_HIP(hipEventSynchronize(w.ev_sel));  // its last reader is done
-                w.sel_pending = false;
-                std::memcpy(w.h_lm_sel.p, sl.lm_mask, (size_t)n_lm);
-                d.sel = w.h_lm_sel_dev;
-            }
-            const Work wk = w.work_at(0);
-            d.pose = wk.pose_init;
-            d.pw = wk.pw_init;
-            if (tri) {
-                if (w.at_initial) w.state_fresh = true;
-            } else if (!w.state_fresh) {
-                const int cur = w.h_state.p->cur;
-                d.pose = wk.pose[cur];
-                d.pw = wk.pw[cur];
-            }
-            const rsvio_landmark_gate& g = *gate[i];
-            d.gate = LmGate{tri ? g.mode : (int)RSVIO_TRI_ALL_VIEWS, g.min_depth, g.max_depth, g.max_sq_error};
-            d.G = w.G;
-            d.Pr = w.prob();
-            d.obs_mask = w.obs_mask_dev();
-            d.pw_out = reinterpret_cast<double*>(w.d_arena.p + w.lay.pw_init);
-            d.info = w.d_lm_info.p;
-            d.skip = 0;
-            max_blocks = std::max(max_blocks, w.G.n_wave + (n_lm + 63) / 64);
-        }
-        if (!max_blocks) return;
-        for (int i = 0; i < B; ++i)
-            if (live[i]) after_window(i);
-        RSVIO_HIP(hipMemcpyAsync(d_lmdesc.p, h_lmdesc.p, sizeof(LmDesc) * B, hipMemcpyHostToDevice, stream));
-        RSVIO_HIP(hipEventRecord(ev_lmcopy, stream));
-        lmcopy_pending = true;
-        RSVIO_HIP(hipEventRecord(ev0, stream));
-        if (tri)
-            hipLaunchKernelGGL(bab_landmarks<true>, dim3(max_blocks, B), dim3(64), 0, stream, d_lmdesc.p);
-        else
-            hipLaunchKernelGGL(bab_landmarks<false>, dim3(max_blocks, B), dim3(64), 0, stream, d_lmdesc.p);
-        RSVIO_HIP(hipGetLastError());
-        RSVIO_HIP(hipEventRecord(ev1, stream));
-        for (int i = 0; i < B; ++i) {
-            if (!live[i]) continue;
-            BundleAdjuster& w = *win[i];
-            w.settled = false;
-            if (h_lmdesc.p[i].sel) {
-                RSVIO_HIP(hipEventRecord(w.ev_sel, stream));
-                w.sel_pending = true;
-            }
-        }
-        if (!want) {
-            // enqueue only: whatever a window's own stream runs next comes after the batch's kernel
-            RSVIO_HIP(hipEventRecord(ev_after, stream));
-            for (int i = 0; i < B; ++i)
-                if (live[i]) RSVIO_HIP(hipStreamWaitEvent(win[i]->stream, ev_after, 0));
-            return;
-        }
-        for (int i = 0; i < B; ++i) {
-            if (!live[i]) continue;
-            BundleAdjuster& w = *win[i];
-            const size_t n_lm = (size_t)w.G.n_lm;
-            if (tri && slots[i].p_W_out)
-                RSVIO_HIP(hipMemcpyAsync(slots[i].p_W_out, h_lmdesc.p[i].pw_out, sizeof(double) * 3 * n_lm,
-                                         hipMemcpyDeviceToHost, stream));
-            RSVIO_HIP(hipMemcpyAsync(w.h_lm_info.p, w.d_lm_info.p, sizeof(rsvio_landmark_info) * n_lm,
-                                     hipMemcpyDeviceToHost, stream));
-        }
-        RSVIO_HIP(hipStreamSynchronize(stream));
-        lmcopy_pending = false;
-        float ms = 0.0f;
-        RSVIO_HIP(hipEventElapsedTime(&ms, ev0, ev1));
-        if (device_ms) *device_ms = ms;
-        for (int i = 0; i < B; ++i) {
-            if (!live[i]) continue;
-            BundleAdjuster& w = *win[i];
-            idle_window(i);
-            const int n_lm = w.G.n_lm;
-            if (slots[i].info_out)
-                std::memcpy(slots[i].info_out, w.h_lm_info.p, sizeof(rsvio_landmark_info) * (size_t)n_lm);
-            int32_t c = 0;
-            for (int l = 0; l < n_lm; ++l) c += (w.h_lm_info.p[l].flags & RSVIO_LM_OK) ? 1 : 0;
-            slots[i].n_ok = c;
-        }
-    }
-
-    // rsvio_ba_batch_covariance: BundleAdjuster::covariance per slot by one launch chain -- K4 and
-    // K4c on a table of each window's covariance views, the camera covariance once per distinct
-    // template among the windows, the landmark covariance -- and two host waits: the statuses and
-    // costs, then the outputs of the windows that report OK.
-    void covariance(const uint8_t* on, double huber_delta, rsvio_ba_cov_slot* slots, double* device_ms) {
-        const std::string what = "rsvio_ba_batch_covariance";
-        const int B = (int)win.size();
-        if (!(huber_delta > 0.0)) throw std::invalid_argument(what + ": huber_delta must be positive");
-        int n_act = 0;
-        for (int i = 0; i < B; ++i) {
-            if (on && !on[i]) continue;
-            const BundleAdjuster& w = *win[i];
-            const std::string slot = what + " (slot " + std::to_string(i) + ")";
-            if (w.sharded()) throw std::invalid_argument(slot + ": not available on a landmark-sharded handle");
-            w.cov_check(slot, huber_delta, slots[i].lm_idx, slots[i].n_sel, slots[i].cov_lm, slots[i].lm_flags);
-            ++n_act;
-        }
-        if (device_ms) *device_ms = 0.0;
-        if (!n_act) return;
-        int max_wave = 1, max_chunk = 1, max_blocks = 1;
-        std::vector<int> tmpl;  // the distinct camera templates, in order of first appearance
-        for (int i = 0; i < B; ++i) {
-            WinDesc& d = h_desc.p[i];
-            CovDesc& c = h_covdesc.p[i];
-            d = WinDesc{};
-            c = CovDesc{};
-            d.skip = 1;
-            if (on && !on[i]) continue;
-            BundleAdjuster& w = *win[i];
-            const BundleAdjuster::CovPlan p = w.cov_plan(huber_delta, slots[i].lm_idx, slots[i].n_sel);
-            d.skip = 0;
-            d.G = p.Gc;
-            d.Pr = p.pr;
-            d.W[0] = d.W[1] = p.wk;
-            d.W[2] = d.W[3] = p.wl;
-            c.O = p.O;
-            c.O.cst = d_cst.p + 2 * i;
-            c.O.cost = d_cost.p + i;
-            c.obs_mask = w.obs_mask_dev();
-            c.sel = p.d_sel;
-            const int nf = w.G.n_free;
-            c.nf = nf <= 10 ? nf : bk_template_nf(nf);
-            if (c.nf > 0 && std::find(tmpl.begin(), tmpl.end(), c.nf) == tmpl.end()) tmpl.push_back(c.nf);
-            max_wave = std::max(max_wave, w.G.n_wave);
-            max_chunk = std::max(max_chunk, w.G.n_chunk);
-            max_blocks = std::max(max_blocks, w.G.n_wave + (w.G.n_lm + 63) / 64);
-        }
-        max_wave = (max_wave + kGrp - 1) / kGrp * kGrp;  // wave w on XCD w % 8 in every window, as run()
-        for (int i = 0; i < B; ++i)
-            if (!h_desc.p[i].skip) after_window(i);
-        RSVIO_HIP(hipMemcpyAsync(d_desc.p, h_desc.p, sizeof(WinDesc) * B, hipMemcpyHostToDevice, stream));
-        RSVIO_HIP(hipMemcpyAsync(d_covdesc.p, h_covdesc.p, sizeof(CovDesc) * B, hipMemcpyHostToDevice, stream));
-        RSVIO_HIP(hipMemsetAsync(d_cst.p, 0, sizeof(int) * 2 * B, stream));
-        RSVIO_HIP(hipEventRecord(ev0, stream));
-        hipLaunchKernelGGL(bab_linearize, dim3(max_wave, B), dim3(64), 0, stream, d_desc.p, 0.0);
-        hipLaunchKernelGGL(bab_schur_chunks, dim3(max_chunk, B), dim3(kSchurThreads), 0, stream, d_desc.p, 0,
-                           LmArgs{1, 0.0, 0.0});
-        for (int nf : tmpl) {
-            auto launch = [&](auto c) {
-                constexpr int NF = decltype(c)::value;
-                hipLaunchKernelGGL(bab_camera_covariance<NF>, dim3(B), dim3(NF <= 10 ? kK5Threads : 64 * kBkWaves), 0,
-                                   stream, d_desc.p, d_covdesc.p);
-            };
-            if (!(dispatch_panel_nf(nf, launch) || dispatch_block_nf(nf, launch)))
-                throw std::logic_error("batched covariance: no camera template for this window size");
-        }
-        hipLaunchKernelGGL(bab_landmark_covariance, dim3(max_blocks, B), dim3(64), 0, stream, d_desc.p, d_covdesc.p);
-        RSVIO_HIP(hipGetLastError());
-        RSVIO_HIP(hipEventRecord(ev1, stream));
-        for (int i = 0; i < B; ++i) {
-            if (h_desc.p[i].skip) continue;
-            win[i]->settled = false;
-            RSVIO_HIP(hipMemsetAsync(win[i]->d_singular.p, 0, sizeof(int), stream));  // K4c may have set it
-        }
-        RSVIO_HIP(hipMemcpyAsync(h_cst.p, d_cst.p, sizeof(int) * 2 * B, hipMemcpyDeviceToHost, stream));
-        RSVIO_HIP(hipMemcpyAsync(h_cost.p, d_cost.p, sizeof(double) * B, hipMemcpyDeviceToHost, stream));
-        RSVIO_HIP(hipStreamSynchronize(stream));
-        float ms = 0.0f;
-        RSVIO_HIP(hipEventElapsedTime(&ms, ev0, ev1));
-        if (device_ms) *device_ms = ms;
-        bool any_ok = false;
-        for (int i = 0; i < B; ++i) {
-            if (h_desc.p[i].skip) continue;
-            BundleAdjuster& w = *win[i];
-            rsvio_ba_cov_slot& sl = slots[i];
-            BundleAdjuster::cov_fill_info(&sl.info, w.G.n_free, h_cst.p + 2 * i, h_cost.p[i], ms);
-            if (sl.info.status != RSVIO_COV_OK) continue;
-            w.cov_fetch(h_covdesc.p[i].O, sl.cov_cc || sl.cov_pose, sl.n_sel, stream);
-            any_ok = true;
-        }
-        if (any_ok) RSVIO_HIP(hipStreamSynchronize(stream));
-        for (int i = 0; i < B; ++i) {
-            if (h_desc.p[i].skip) continue;
-            const rsvio_ba_cov_slot& sl = slots[i];
-            if (sl.info.status == RSVIO_COV_OK)
-                win[i]->cov_deliver(sl.cov_cc, sl.cov_pose, sl.lm_idx, sl.n_sel, sl.cov_lm, sl.lm_flags);
-            idle_window(i);
-        }
-    }
-};
+// batched mode over B window handles (BundleBatch)
+#include "ba_batch.hpp"
 
 }  // namespace rsvio
 
