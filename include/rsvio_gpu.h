@@ -125,6 +125,14 @@ int rsvio_build_pyramid(const uint8_t* img, int32_t w, int32_t h, int32_t levels
 int rsvio_track_points(const uint8_t* pyr0, const uint8_t* pyr1, int32_t w, int32_t h,
                        int32_t levels, const float* aff_in, int32_t n, int32_t max_iterations,
                        float thresh, float* aff_out, uint8_t* valid_out);
+/* rsvio_track_points with the search of feature i started at seeds[i] (n x 2 f32 pixels of the second
+ * image) instead of its own position -- motion-predicted tracking, see rsvio_tracker_set_prediction
+ * for the rule.  A non-finite seed is replaced by the feature's own position; with every seed equal
+ * to its feature's position the results are rsvio_track_points' bit for bit.  Same contract
+ * otherwise (host buffers; n = 0 is allowed). */
+int rsvio_track_points_seeded(const uint8_t* pyr0, const uint8_t* pyr1, int32_t w, int32_t h,
+                              int32_t levels, const float* aff_in, const float* seeds, int32_t n,
+                              int32_t max_iterations, float thresh, float* aff_out, uint8_t* valid_out);
 /* detect_key_points(img, grid, current, 1) (image_utilities.rs:108-175) with the existing
  * tracks' positions (rounded as feature_tracker.rs:232-233).  out_xy: u32 (x, y) pairs. */
 int rsvio_detect_keypoints(const uint8_t* img, int32_t w, int32_t h, int32_t grid,
@@ -266,6 +274,15 @@ int rsvio_unproject(const rsvio_camera* cam, const float* px, size_t n, float* o
 /* Same on device pointers, enqueued on `stream` (hipStream_t; NULL = legacy stream). */
 int rsvio_unproject_d(const rsvio_camera* cam, const float* d_px, size_t n, float* d_out_xy,
                       uint8_t* d_valid_out, void* stream);
+/* The forward projection of the same models: camera-frame points (n x 3 f64) -> pixels (n x 2 f64),
+ * with distortion, in f64 without contraction.
+ *   EUCM    den = alpha sqrt(beta (X*X + Y*Y) + Z*Z) + (1 - alpha) Z, valid iff den > 0
+ *   radtan  valid iff Z > 0; k3 included
+ * An invalid point gives NaN coordinates and valid_out = 0 (valid_out may be NULL); n = 0 is a no-op
+ * that returns RSVIO_OK.  Host buffers, current device; _d: device pointers, enqueued on `stream`. */
+int rsvio_project(const rsvio_camera* cam, const double* pts, size_t n, double* out_uv, uint8_t* valid_out);
+int rsvio_project_d(const rsvio_camera* cam, const double* d_pts, size_t n, double* d_out_uv,
+                    uint8_t* d_valid_out, void* stream);
 /* Frame::add_left_feature / add_right_feature on the tracker's output: after this call every
  * process_frame also unprojects both cameras' features on device (fused into the output
  * packing) and rsvio_tracker_undistorted returns them in feature order.  NULL, NULL turns it
@@ -897,6 +914,53 @@ int rsvio_stereo_gate_lists(const rsvio_stereo_gate* gate, int32_t convention_l,
                             const uint64_t* ids_l, const float* uv_l, size_t n_l,
                             const uint64_t* ids_r, const float* uv_r, size_t n_r,
                             uint8_t* keep_l, uint8_t* keep_r, double* err_r, rsvio_gate_counts* counts);
+
+/* Motion-predicted tracking: the LK search of a feature started where a rotation hint says it went.
+ * track_one_point (feature_tracker.rs:292-342) starts the search in the new image at the feature's
+ * position in the old one; with a few pyramid levels the capture range is a few pixels at the
+ * coarsest level, so a camera that yaws a few degrees between frames loses almost every track.  A
+ * rotation hint R = R_cur_prev (a bearing in the current camera frame is R times the bearing in the
+ * previous one: an integrated gyro, or the last inter-frame rotation) moves each feature's start.
+ *   Seed of a feature at pixel (u, v) of a camera:
+ *     (x, y, ok) = the fused unprojection of (u, v) (the stored f32 values)
+ *     b = (x, y, 1) (RSVIO_UNPROJ_PLANE) or (x, y, sqrt(max(0, (1 - x*x) - y*y))) (RSVIO_UNPROJ_RAY), f64
+ *     q = R b, row-major, each row summed left to right
+ *     (u', v') = rsvio_project's projection of q, narrowed to f32
+ *   seeded iff ok, the projection is valid, both values are finite, 0 <= u' <= w - 1 and
+ *   0 <= v' <= h - 1; otherwise the seed is (u, v) itself and the feature counts as unseeded.
+ *   Seeded LK (rsvio_track_points_seeded, and the handle's frame): the forward pass builds its
+ * templates at the feature's position as before and starts its search at the seed; the backward pass
+ * (images swapped, templates at the forward result fwd) starts at fwd.t - (seed - t0), the inverse
+ * prediction; the result is accepted by the same test |t0 - bwd.t|^2 < 0.4.
+ *   rsvio_predict_seeds: the seeds of n pixels (host buffers, current device; _d: device pointers,
+ * enqueued on `stream`); seeded_out: 1 / 0 per entry.  RSVIO_ERR_INVALID_ARG when
+ * max |R^T R - I| > 1e-6 or det R < 0.
+ *   rsvio_tracker_set_prediction: the hint of both cameras for EXACTLY the next frame enqueued on the
+ * handle (process_frame*, or submit* with collect); that enqueue clears it.  NULL clears a pending
+ * one.  Off by default: a handle without a pending prediction launches exactly what it launched
+ * before.  It needs rsvio_tracker_set_cameras (RSVIO_ERR_INVALID_ARG without; detaching the cameras
+ * clears a pending prediction) and validates both rotations as rsvio_predict_seeds does.  It is host
+ * state: it may be set while a frame is in flight and then applies to the next submit.  On a
+ * handle's first frame it is consumed without effect.  The predicted frame costs one extra launch
+ * (the seeds of both maps) and no extra host wait; the new corners' stereo jobs, the append / pack
+ * and the stereo gate are unchanged.
+ *   rsvio_tracker_prediction_report: the last collected frame: per camera how many entries of the
+ * previous frame's lists were seeded / unseeded (all 0 when that frame had no prediction) and, when
+ * seeds_l / seeds_r are given (n x 2 f32, capacities in entries), the seeds in the order of the
+ * previous frame's lists; a capacity below the list's length truncates and returns
+ * RSVIO_ERR_CAPACITY.  An on-demand read-back with its own wait, from the collected frame's own
+ * buffer (a frame submitted since writes another).  counts may be NULL.
+ *   rsvio_tracker_batch_process_frames does not seed: a batch holding a handle with a pending
+ * prediction is refused (RSVIO_ERR_INVALID_ARG, nothing enqueued, the prediction stays pending). */
+typedef struct { double R_l[9]; double R_r[9]; } rsvio_track_prediction;          /* 144 bytes; row-major R_cur_prev */
+typedef struct { int32_t n_seeded[2]; int32_t n_unseeded[2]; } rsvio_prediction_counts;   /* 16 bytes; [left, right] */
+int rsvio_predict_seeds(const rsvio_camera* cam, const double* R, const float* px, size_t n,
+                        int32_t w, int32_t h, float* seeds_out, uint8_t* seeded_out);
+int rsvio_predict_seeds_d(const rsvio_camera* cam, const double* R, const float* d_px, size_t n,
+                          int32_t w, int32_t h, float* d_seeds_out, uint8_t* d_seeded_out, void* stream);
+int rsvio_tracker_set_prediction(rsvio_tracker* t, const rsvio_track_prediction* pred);
+int rsvio_tracker_prediction_report(rsvio_tracker* t, rsvio_prediction_counts* counts,
+                                    float* seeds_l, size_t cap_l, float* seeds_r, size_t cap_r);
 
 #ifdef __cplusplus
 }

@@ -86,4 +86,42 @@ __device__ __forceinline__ Undist unproject_one(const rsvio_camera& cam, float u
     return r;
 }
 
+// The forward projection of the same two models: a camera-frame point (X, Y, Z) -> pixel, with
+// distortion.  Formulas, operation order and validity rules of oracle/camera_oracle.cpp's
+// project(): EUCM den = alpha sqrt(beta (X^2 + Y^2) + Z^2) + (1 - alpha) Z, valid iff den > 0;
+// radtan valid iff Z > 0, k3 included.  f64 throughout (bit-exact with the oracle); an invalid
+// point gives NaN.
+struct Proj {
+    double u, v;
+    bool ok;
+};
+
+__device__ __forceinline__ Proj project_one(const rsvio_camera& cam, double X, double Y, double Z) {
+    const double* p = cam.params;
+    Proj r;
+    r.u = r.v = __builtin_nan("");
+    r.ok = false;
+    if (cam.model == RSVIO_CAM_EUCM) {
+        const double alpha = p[4], beta = p[5];
+        const double d = sqrt(beta * (X * X + Y * Y) + Z * Z);
+        const double den = alpha * d + (1.0 - alpha) * Z;
+        if (!(den > 0.0)) return r;
+        r.u = p[0] * (X / den) + p[2];
+        r.v = p[1] * (Y / den) + p[3];
+        r.ok = true;
+        return r;
+    }
+    if (!(Z > 0.0)) return r;
+    const double x = X / Z, y = Y / Z;
+    const double k1 = p[4], k2 = p[5], p1 = p[6], p2 = p[7], k3 = p[8];
+    const double x2 = x * x, y2 = y * y, xy = x * y, r2 = x2 + y2;
+    const double rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3));
+    const double xd = x * rad + 2.0 * p1 * xy + p2 * (r2 + 2.0 * x2);
+    const double yd = y * rad + p1 * (r2 + 2.0 * y2) + 2.0 * p2 * xy;
+    r.u = p[0] * xd + p[2];
+    r.v = p[1] * yd + p[3];
+    r.ok = true;
+    return r;
+}
+
 }  // namespace rsvio

@@ -409,9 +409,12 @@ __device__ bool track_at_level(const LevelImg& im, const Template& T, float patx
 // track_one_point (feature_tracker.rs:292-342): the L templates first (make_templates), then
 // the levels coarse to fine; an invalid template fails the call when its level is reached, as
 // the reference's level-by-level build does.
-template <int L>
+// SEEDED (lk_track_seeded_kernel): the search starts at (sx, sy) instead of T0's translation; the
+// templates, the levels and the product are the same.
+template <int L, bool SEEDED = false>
 __device__ bool track_one(const uint8_t* pyr0, const uint8_t* pyr1, uint32_t w, uint32_t h, const Aff& T0, int lane,
-                          float patx, float paty, int max_iter, float thresh, Aff& out, float* sh, float* tsh) {
+                          float patx, float paty, int max_iter, float thresh, Aff& out, float* sh, float* tsh,
+                          float sx = 0.0f, float sy = 0.0f) {
     uint32_t tok_mask = 0;
     {
         Template tp[L];
@@ -434,8 +437,8 @@ __device__ bool track_one(const uint8_t* pyr0, const uint8_t* pyr1, uint32_t w, 
     Aff T1;
     T1.m00 = 1.0f; T1.m01 = 0.0f; T1.m10 = 0.0f; T1.m11 = 1.0f;
     T1.m20 = 0.0f; T1.m21 = 0.0f; T1.m22 = 1.0f;
-    T1.m02 = T0.m02;
-    T1.m12 = T0.m12;
+    T1.m02 = SEEDED ? sx : T0.m02;
+    T1.m12 = SEEDED ? sy : T0.m12;
 #pragma unroll 1
     for (int i = L - 1; i >= 0; --i) {
         const float sdn = (float)(1 << i);
@@ -538,6 +541,93 @@ __global__ __launch_bounds__(64) void lk_track_kernel(TrackLaunch P) {
     }
 }
 
+// lk_track_kernel with a start position per feature (motion-predicted tracking):
+// the same job mapping, templates and levels.  Forward: the templates at T0's position, the search
+// started at the seed.  Backward: the images swapped, the templates at fwd, the search started at
+// the inverse prediction bs = fwd.t - (seed - T0.t) -- started at fwd.t it fails for the reason the
+// unseeded forward pass does.  Accepted by the same squared-distance test against T0.  A batch
+// without seeds (null pointer) and a non-finite seed start at the feature's own position, where
+// every value is lk_track_kernel's (seed - T0.t = 0, so bs = fwd.t).
+template <int L>
+__global__ __launch_bounds__(64) void lk_track_seeded_kernel(TrackLaunch P, TrackSeeds S) {
+    const int per = (P.njobs + kXcds - 1) / kXcds;
+    const int job = (int)(blockIdx.x % kXcds) * per + (int)(blockIdx.x / kXcds);
+    if (job >= P.njobs) return;
+    const uint8_t* pyr0;
+    const uint8_t* pyr1;
+    const float* ain;
+    const float* seeds;
+    float* aout;
+    uint8_t* valid;
+    int idx;
+    if (P.table != nullptr) {
+        int lo = 0, hi = P.nb - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (P.tstart[mid] <= job) lo = mid; else hi = mid - 1;
+        }
+        const rsvio_track_batch& d = P.table[lo];
+        idx = job - P.tstart[lo];
+        if (idx < 0 || idx >= d.n) return;
+        pyr0 = d.d_pyr0; pyr1 = d.d_pyr1; ain = d.d_aff_in; aout = d.d_aff_out; valid = d.d_valid;
+        seeds = S.tseed != nullptr ? S.tseed[lo] : nullptr;
+        if (P.tmask != nullptr) {
+            const int4* m = P.tmask[lo];
+            if (m != nullptr && m[idx].w == 0) {
+                if (threadIdx.x == 0) valid[idx] = 0;
+                return;
+            }
+        }
+    } else {
+        int b = 0;
+        while (b + 1 < P.nb && job >= P.start[b + 1]) ++b;
+        idx = job - P.start[b];
+        if (P.dcount[b] != nullptr && idx >= *P.dcount[b]) return;
+        pyr0 = P.pyr0[b]; pyr1 = P.pyr1[b]; ain = P.ain[b]; aout = P.aout[b]; valid = P.valid[b];
+        seeds = S.seed[b];
+        if (P.mask[b] != nullptr && P.mask[b][idx].w == 0) {
+            if (threadIdx.x == 0) valid[idx] = 0;
+            return;
+        }
+    }
+    __shared__ __attribute__((aligned(16))) float sh[6 * (L < 4 ? L : 4) * kChainLd];
+    __shared__ float tsh[4 * L * 64];
+    const int lane = threadIdx.x;
+    const float patx = lane < NP ? (float)kPattern[lane][0] / 2.0f : 0.0f;
+    const float paty = lane < NP ? (float)kPattern[lane][1] / 2.0f : 0.0f;
+    const float* a = ain + 6 * (size_t)idx;
+    Aff T0;
+    T0.m00 = a[0]; T0.m01 = a[1]; T0.m10 = a[2]; T0.m11 = a[3]; T0.m02 = a[4]; T0.m12 = a[5];
+    T0.m20 = 0.0f; T0.m21 = 0.0f; T0.m22 = 1.0f;
+    float sx = T0.m02, sy = T0.m12;
+    if (seeds != nullptr) {
+        const float qx = seeds[2 * (size_t)idx], qy = seeds[2 * (size_t)idx + 1];
+        if (isfinite(qx) && isfinite(qy)) {
+            sx = qx;
+            sy = qy;
+        }
+    }
+    Aff fwd, bwd;
+    bool ok = track_one<L, true>(pyr0, pyr1, P.w, P.h, T0, lane, patx, paty, P.max_iter, P.thresh, fwd, sh, tsh, sx, sy);
+    if (ok) {
+        const float bx = fwd.m02 - (sx - T0.m02), by = fwd.m12 - (sy - T0.m12);
+        ok = track_one<L, true>(pyr1, pyr0, P.w, P.h, fwd, lane, patx, paty, P.max_iter, P.thresh, bwd, sh, tsh, bx, by);
+    }
+    if (ok) {
+        float dx = T0.m02 - bwd.m02, dy = T0.m12 - bwd.m12;
+        ok = (dx * dx + dy * dy) < 0.4f;
+    }
+    if (lane == 0) {
+        float* o = aout + 6 * (size_t)idx;
+        if (ok) {
+            o[0] = fwd.m00; o[1] = fwd.m01; o[2] = fwd.m10; o[3] = fwd.m11; o[4] = fwd.m02; o[5] = fwd.m12;
+        } else {
+            for (int k = 0; k < 6; ++k) o[k] = a[k];
+        }
+        valid[idx] = ok ? 1 : 0;
+    }
+}
+
 }  // namespace
 
 RSVIO_DBG_READER(rsvio_dbg_lk_stamps)
@@ -554,6 +644,22 @@ void enqueue_track(const TrackLaunch& L0, hipStream_t s) {
         RSVIO_LK(1) RSVIO_LK(2) RSVIO_LK(3) RSVIO_LK(4) RSVIO_LK(5) RSVIO_LK(6) RSVIO_LK(7) RSVIO_LK(8)
 #undef RSVIO_LK
         default: throw std::invalid_argument("track_points: levels must be in [1, 8]");
+    }
+    RSVIO_HIP(hipGetLastError());
+}
+
+void enqueue_track_seeded(const TrackLaunch& L0, const TrackSeeds& S, hipStream_t s) {
+    TrackLaunch L = L0;
+    const int total = L.table != nullptr ? L.start[0] : L.start[L.nb];
+    if (total <= 0) return;
+    L.njobs = total;
+    const int grid = ((total + kXcds - 1) / kXcds) * kXcds;
+    switch (L.levels) {
+#define RSVIO_LK(NL) \
+    case NL: hipLaunchKernelGGL(lk_track_seeded_kernel<NL>, dim3(grid), dim3(64), 0, s, L, S); break;
+        RSVIO_LK(1) RSVIO_LK(2) RSVIO_LK(3) RSVIO_LK(4) RSVIO_LK(5) RSVIO_LK(6) RSVIO_LK(7) RSVIO_LK(8)
+#undef RSVIO_LK
+        default: throw std::invalid_argument("track_points_seeded: levels must be in [1, 8]");
     }
     RSVIO_HIP(hipGetLastError());
 }

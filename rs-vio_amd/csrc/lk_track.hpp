@@ -34,4 +34,14 @@ struct TrackLaunch {
 
 void enqueue_track(const TrackLaunch& L, hipStream_t s);
 
+// Seeded launch (lk_track_seeded_kernel): the same jobs, each feature's search started at a seed
+// instead of its own position.  A launch argument of its own beside TrackLaunch, so the unseeded
+// kernels' argument block is what it was.
+struct TrackSeeds {
+    const float* seed[kMaxTrackBatches];  // per batch: n x 2 f32 start positions; null: its own position
+    const float* const* tseed;            // table mode: a device array of nb seed pointers (null entry: as above)
+};
+
+void enqueue_track_seeded(const TrackLaunch& L, const TrackSeeds& S, hipStream_t s);
+
 }  // namespace rsvio

@@ -14,6 +14,8 @@
 //      cam0 track in cell scan order with consecutive ids, pack (+ unprojection) (1 workgroup);
 //      with a stereo gate set on the handle (tracker_gate.hpp), the epipolar check of the frame's
 //      pairs and the compaction of the rejected ones, between the append and the packing
+// With a pending prediction (rsvio_tracker_set_prediction, tracker_predict.hpp) the frame has one launch
+// more, between K1 and K2: the seeds of both maps from the rotation hint; K2 is then the seeded kernel.
 // The reference detects only in the cells its surviving tracks leave empty and then tracks those
 // corners; a cell's corner and its stereo track depend on nothing but the cell and the images,
 // so detecting and tracking every cell up front and dropping the occupied ones afterwards gives
@@ -107,6 +109,7 @@ struct CamPair {
 };
 
 #include "tracker_gate.hpp"
+#include "tracker_predict.hpp"
 
 // The end of process_frame in one workgroup: (1) the surviving temporal tracks of each camera
 // compacted in order from the tracker's output (at, valid) into the track map (feature_tracker.rs
@@ -371,6 +374,16 @@ struct Tracker {
     DevBuf<uint64_t> rep_ids;       // the rejected ids, one list per output slot (2 x cap): gate_report()
     DevBuf<double> rep_err;         // reads the collected frame's, the next frame writes the other
     rsvio_gate_counts rep_counts{}; // of the last collected frame
+    // motion-predicted tracking (rsvio_tracker_set_prediction): a pending prediction is host state and
+    // applies to exactly the next frame enqueued; its buffers are allocated when one is first set
+    rsvio_track_prediction pred{};
+    bool pred_pending = false;
+    DevBuf<float2> pred_seeds;      // the frame's seeds, one list per output slot and camera (2 x 2 x cap):
+    DevBuf<uint8_t> pred_flags;     // prediction_report() reads the collected frame's, the next frame writes the other
+    bool pred_on[2] = {false, false};       // per output slot: its frame was tracked from seeds
+    int pred_n[2][2] = {{0, 0}, {0, 0}};    // ... over this many entries of the previous frame's lists
+    float2* pseed(int slot, int c) { return pred_seeds.p + (size_t)(2 * slot + c) * cap; }
+    uint8_t* pflag(int slot, int c) { return pred_flags.p + (size_t)(2 * slot + c) * cap; }
 
     bool gated() const { return gate.mode != RSVIO_GATE_OFF; }
     GateDev gate_dev(int slot) {
@@ -460,6 +473,29 @@ struct Tracker {
         io.src[1] = d_right; io.dst[1] = pyr(nxt, 1);
         io.fast_cells = n_cells; io.fg = G; io.fast_pt = cell_pt.p; io.fast_aff = new_aff.p;
         plan.enqueue(io, 2, stream);
+        // a pending prediction is consumed by this frame (on a first frame, without effect): the seeds
+        // of both maps in one launch, into the frame's output slot
+        const bool seeded = pred_pending && has_prev && cams.on;
+        pred_pending = false;
+        pred_on[wslot] = seeded;
+        pred_n[wslot][0] = seeded ? host_count[0] : 0;
+        pred_n[wslot][1] = seeded ? host_count[1] : 0;
+        if (seeded && host_count[0] + host_count[1] > 0) {
+            PredictArgs A{};
+            for (int c = 0; c < 2; ++c) {
+                A.cam[c] = cams.cam[c];
+                std::memcpy(A.R[c], c == 0 ? pred.R_l : pred.R_r, sizeof(double) * 9);
+                A.pos[c] = maff(c);
+                A.seeds[c] = pseed(wslot, c);
+                A.seeded[c] = pflag(wslot, c);
+                A.n[c] = host_count[c];
+            }
+            A.stride = 6; A.off = 4;
+            A.w = P.width; A.h = P.height;
+            hipLaunchKernelGGL(predict_seeds_kernel, dim3((host_count[0] + host_count[1] + 255) / 256), dim3(256), 0,
+                               stream, A);
+            RSVIO_HIP(hipGetLastError());
+        }
         {  // one LK launch: [cam0 temporal, cam1 temporal,] stereo of every cell's corner
             TrackLaunch L{};
             L.w = P.width; L.h = P.height; L.levels = P.levels; L.max_iter = P.max_iterations;
@@ -478,7 +514,14 @@ struct Tracker {
             L.mask[b] = cell_pt.p;  // cells without a corner exit at once
             L.start[b + 1] = L.start[b] + n_cells;
             L.nb = b + 1;
-            enqueue_track(L, stream);
+            if (seeded) {  // the temporal batches from their seeds; the new corners' stereo batch from its own positions
+                TrackSeeds S{};
+                S.seed[0] = reinterpret_cast<const float*>(pseed(wslot, 0));
+                S.seed[1] = reinterpret_cast<const float*>(pseed(wslot, 1));
+                enqueue_track_seeded(L, S, stream);
+            } else {
+                enqueue_track(L, stream);
+            }
         }
         if (!gated())
             hipLaunchKernelGGL(append_pack_kernel, dim3(1), dim3(1024), 0, stream, G, bins.p, host_count[0],
@@ -788,6 +831,7 @@ int rsvio_tracker_set_cameras(rsvio_tracker* t, const rsvio_camera* left, const 
             if (T.gated())
                 throw std::invalid_argument("rsvio_tracker_set_cameras: a stereo gate is set (turn it off first)");
             T.cams.on = 0;
+            T.pred_pending = false;  // (a prediction needs the cameras)
             T.last_n[0] = T.last_n[1] = 0;
             return (int)RSVIO_OK;
         }
@@ -1026,6 +1070,133 @@ int rsvio_dbg_stereo_gate_frame(const rsvio_stereo_gate* gate, int32_t conventio
     });
 }
 
+namespace {
+// A rotation hint is refused when max |R^T R - I| > 1e-6 (NaN included) or det R < 0
+static void check_rotation(const char* who, const char* name, const double* R) {
+    bool ortho = true;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const double v = R[i] * R[j] + R[3 + i] * R[3 + j] + R[6 + i] * R[6 + j];
+            ortho = ortho && std::fabs(v - (i == j ? 1.0 : 0.0)) <= 1e-6;  // (false for a NaN)
+        }
+    const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) +
+                       R[2] * (R[3] * R[7] - R[4] * R[6]);
+    if (!ortho || !(det > 0.0))
+        throw std::invalid_argument(std::string(who) + ": " + name + " is not a rotation (|R^T R - I| > 1e-6 or det < 0)");
+}
+
+// predict_seeds_kernel over one list of pixel pairs
+static void enqueue_predict(const rsvio_camera& cam, const double* R, const float* d_px, int n, int w, int h,
+                            float* d_seeds, uint8_t* d_seeded, hipStream_t s) {
+    if (n <= 0) return;
+    rsvio::PredictArgs A{};
+    A.cam[0] = A.cam[1] = cam;
+    std::memcpy(A.R[0], R, sizeof(double) * 9);
+    A.pos[0] = d_px;
+    A.seeds[0] = reinterpret_cast<float2*>(d_seeds);
+    A.seeded[0] = d_seeded;
+    A.n[0] = n;
+    A.stride = 2; A.off = 0;
+    A.w = w; A.h = h;
+    hipLaunchKernelGGL(rsvio::predict_seeds_kernel, dim3((n + 255) / 256), dim3(256), 0, s, A);
+    RSVIO_HIP(hipGetLastError());
+}
+
+static bool predict_args_ok(const char* who, const rsvio_camera* cam, const double* R, const void* px, size_t n,
+                            int32_t w, int32_t h, const void* seeds, const void* seeded) {
+    if (!rsvio::camera_ok(cam) || !R || w < 1 || h < 1 || n > (size_t)1 << 30 || (n && (!px || !seeds || !seeded))) {
+        rsvio::set_last_error(std::string(who) + ": invalid camera, rotation, size or buffers");
+        return false;
+    }
+    return true;
+}
+}  // namespace
+
+int rsvio_predict_seeds(const rsvio_camera* cam, const double* R, const float* px, size_t n, int32_t w, int32_t h,
+                        float* seeds_out, uint8_t* seeded_out) {
+    if (!predict_args_ok("rsvio_predict_seeds", cam, R, px, n, w, h, seeds_out, seeded_out)) return RSVIO_ERR_INVALID_ARG;
+    return guarded([&] {
+        check_rotation("rsvio_predict_seeds", "R", R);
+        if (n == 0) return (int)RSVIO_OK;
+        rsvio::DevBuf<float> dp(2 * n), ds(2 * n);
+        rsvio::DevBuf<uint8_t> df(n);
+        RSVIO_HIP(hipMemcpy(dp.p, px, sizeof(float) * 2 * n, hipMemcpyHostToDevice));
+        enqueue_predict(*cam, R, dp.p, (int)n, w, h, ds.p, df.p, nullptr);
+        RSVIO_HIP(hipMemcpy(seeds_out, ds.p, sizeof(float) * 2 * n, hipMemcpyDeviceToHost));
+        RSVIO_HIP(hipMemcpy(seeded_out, df.p, n, hipMemcpyDeviceToHost));
+        return (int)RSVIO_OK;
+    });
+}
+
+int rsvio_predict_seeds_d(const rsvio_camera* cam, const double* R, const float* d_px, size_t n, int32_t w, int32_t h,
+                          float* d_seeds_out, uint8_t* d_seeded_out, void* stream) {
+    if (!predict_args_ok("rsvio_predict_seeds_d", cam, R, d_px, n, w, h, d_seeds_out, d_seeded_out))
+        return RSVIO_ERR_INVALID_ARG;
+    return guarded([&] {
+        check_rotation("rsvio_predict_seeds_d", "R", R);
+        enqueue_predict(*cam, R, d_px, (int)n, w, h, d_seeds_out, d_seeded_out, static_cast<hipStream_t>(stream));
+        return (int)RSVIO_OK;
+    });
+}
+
+int rsvio_tracker_set_prediction(rsvio_tracker* t, const rsvio_track_prediction* pred) {
+    if (!t) return RSVIO_ERR_INVALID_ARG;
+    return guarded([&] {
+        auto& T = t->t;
+        const char* who = "rsvio_tracker_set_prediction";
+        if (!pred) {
+            T.pred_pending = false;
+            return (int)RSVIO_OK;
+        }
+        if (!T.cams.on) throw std::invalid_argument(std::string(who) + ": no cameras attached (rsvio_tracker_set_cameras)");
+        check_rotation(who, "R_l", pred->R_l);
+        check_rotation(who, "R_r", pred->R_r);
+        if (!T.pred_seeds.p) {
+            RSVIO_HIP(hipSetDevice(T.P.device));
+            T.pred_seeds.alloc((size_t)4 * T.cap);
+            T.pred_flags.alloc((size_t)4 * T.cap);
+        }
+        T.pred = *pred;
+        T.pred_pending = true;
+        return (int)RSVIO_OK;
+    });
+}
+
+int rsvio_tracker_prediction_report(rsvio_tracker* t, rsvio_prediction_counts* counts, float* seeds_l, size_t cap_l,
+                                    float* seeds_r, size_t cap_r) {
+    if (!t || (cap_l && !seeds_l) || (cap_r && !seeds_r)) return RSVIO_ERR_INVALID_ARG;
+    return guarded([&] {
+        auto& T = t->t;
+        rsvio_prediction_counts c{};
+        const int slot = T.rslot;
+        bool truncated = false;
+        if (T.pred_on[slot]) {
+            // the collected frame's slot was complete when its frame was collected; a frame submitted
+            // since writes the other slot on the handle's stream, which these copies do not wait for
+            RSVIO_HIP(hipSetDevice(T.P.device));
+            float* out[2] = {seeds_l, seeds_r};
+            const size_t cp[2] = {cap_l, cap_r};
+            std::vector<uint8_t> f;
+            for (int k = 0; k < 2; ++k) {
+                const size_t n = (size_t)T.pred_n[slot][k];
+                f.assign(n, 0);
+                if (n) RSVIO_HIP(hipMemcpy(f.data(), T.pflag(slot, k), n, hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < n; ++i) (f[i] ? c.n_seeded : c.n_unseeded)[k] += 1;
+                if (!out[k]) continue;
+                const size_t m = std::min(n, cp[k]);
+                if (m) RSVIO_HIP(hipMemcpy(out[k], T.pseed(slot, k), m * sizeof(float2), hipMemcpyDeviceToHost));
+                truncated = truncated || m < n;
+            }
+        }
+        if (counts) *counts = c;
+        if (truncated) {
+            rsvio::set_last_error("rsvio_tracker_prediction_report: more seeds than the output capacity (truncated)");
+            return (int)RSVIO_ERR_CAPACITY;
+        }
+        return (int)RSVIO_OK;
+    });
+}
+
 int rsvio_tracker_remove_ids(rsvio_tracker* t, const uint64_t* ids, size_t n) {
     if (!t || (!ids && n)) return RSVIO_ERR_INVALID_ARG;
     if (n == 0) return RSVIO_OK;
@@ -1158,6 +1329,38 @@ int rsvio_track_points(const uint8_t* pyr0, const uint8_t* pyr1, int32_t w, int3
         L.pyr0[0] = d0.p; L.pyr1[0] = d1.p; L.ain[0] = ai.p; L.aout[0] = ao.p; L.valid[0] = dv.p;
         L.dcount[0] = nullptr;
         rsvio::enqueue_track(L, nullptr);
+        if (n) {
+            RSVIO_HIP(hipMemcpy(aff_out, ao.p, sizeof(float) * 6 * n, hipMemcpyDeviceToHost));
+            RSVIO_HIP(hipMemcpy(valid_out, dv.p, n, hipMemcpyDeviceToHost));
+        }
+        return (int)RSVIO_OK;
+    });
+}
+
+int rsvio_track_points_seeded(const uint8_t* pyr0, const uint8_t* pyr1, int32_t w, int32_t h, int32_t levels,
+                              const float* aff_in, const float* seeds, int32_t n, int32_t max_iterations, float thresh,
+                              float* aff_out, uint8_t* valid_out) {
+    if (!pyr0 || !pyr1 || n < 0 || (n > 0 && (!aff_in || !seeds || !aff_out || !valid_out))) return RSVIO_ERR_INVALID_ARG;
+    if (levels < 1 || levels > rsvio::kMaxLevels || w < 1 || h < 1) return RSVIO_ERR_INVALID_ARG;
+    return guarded([&] {
+        const size_t pb = rsvio::level_offset(w, h, levels);
+        const size_t m = (size_t)std::max(n, 1);
+        rsvio::DevBuf<uint8_t> d0(pb), d1(pb), dv(m);
+        rsvio::DevBuf<float> ai(m * 6), ao(m * 6), sd(m * 2);
+        RSVIO_HIP(hipMemcpy(d0.p, pyr0, pb, hipMemcpyHostToDevice));
+        RSVIO_HIP(hipMemcpy(d1.p, pyr1, pb, hipMemcpyHostToDevice));
+        if (n) {
+            RSVIO_HIP(hipMemcpy(ai.p, aff_in, sizeof(float) * 6 * n, hipMemcpyHostToDevice));
+            RSVIO_HIP(hipMemcpy(sd.p, seeds, sizeof(float) * 2 * n, hipMemcpyHostToDevice));
+        }
+        rsvio::TrackLaunch L{};
+        L.w = w; L.h = h; L.levels = levels; L.max_iter = max_iterations; L.thresh = thresh; L.nb = 1;
+        L.start[0] = 0; L.start[1] = n;
+        L.pyr0[0] = d0.p; L.pyr1[0] = d1.p; L.ain[0] = ai.p; L.aout[0] = ao.p; L.valid[0] = dv.p;
+        L.dcount[0] = nullptr;
+        rsvio::TrackSeeds S{};
+        S.seed[0] = sd.p;
+        rsvio::enqueue_track_seeded(L, S, nullptr);
         if (n) {
             RSVIO_HIP(hipMemcpy(aff_out, ao.p, sizeof(float) * 6 * n, hipMemcpyDeviceToHost));
             RSVIO_HIP(hipMemcpy(valid_out, dv.p, n, hipMemcpyDeviceToHost));

@@ -181,6 +181,10 @@ struct TrackerBatch {
             if ((f[i].cap_l && !f[i].out_l) || (f[i].cap_r && !f[i].out_r))
                 throw std::invalid_argument(at + "NULL list with a capacity");
             if (T[i]->inflight) throw CallOrderError(at + "a frame is in flight on this handle (collect it first)");
+            // (the batched launch tracks every feature from its own position: the prediction stays pending)
+            if (T[i]->pred_pending)
+                throw std::invalid_argument(at + "a prediction is pending on this handle (rsvio_tracker_set_prediction; "
+                                                 "the batched call does not seed)");
         }
     }
 
@@ -324,6 +328,8 @@ struct TrackerBatch {
             const int slot = t.wslot;
             t.wslot ^= 1;
             t.rslot = slot;
+            t.pred_on[slot] = false;  // (an unpredicted frame: prediction_report gives zeros)
+            t.pred_n[slot][0] = t.pred_n[slot][1] = 0;
             t.host_count[0] = head[0];
             t.host_count[1] = head[1];
             t.set_report(head + 4);

@@ -128,6 +128,16 @@ class GateCounts(C.Structure):
 GATE_MODES = {"off": 0, "drop_right": 1, "drop_both": 2}
 
 
+class TrackPrediction(C.Structure):
+    """rsvio_track_prediction (144 B): the rotation hint R_cur_prev of each camera, row-major."""
+    _fields_ = [("R_l", C.c_double * 9), ("R_r", C.c_double * 9)]
+
+
+class PredictionCounts(C.Structure):
+    """rsvio_prediction_counts (16 B): a predicted frame's seeded / unseeded entries, [left, right]."""
+    _fields_ = [("n_seeded", C.c_int32 * 2), ("n_unseeded", C.c_int32 * 2)]
+
+
 class BaParams(C.Structure):
     _fields_ = [("max_keyframes", C.c_int32), ("max_landmarks", C.c_int32),
                 ("max_observations", C.c_int32), ("device", C.c_int32)]
@@ -242,6 +252,14 @@ SIG = {
     "rsvio_tracker_gate_report": (C.c_int, [P, C.POINTER(GateCounts), P, P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "rsvio_stereo_gate_lists": (C.c_int, [C.POINTER(StereoGate), C.c_int32, C.c_int32, P, P, C.c_size_t, P, P,
                                           C.c_size_t, P, P, P, C.POINTER(GateCounts)]),
+    "rsvio_project": (C.c_int, [C.POINTER(Camera), P, C.c_size_t, P, P]),
+    "rsvio_project_d": (C.c_int, [C.POINTER(Camera), P, C.c_size_t, P, P, P]),
+    "rsvio_predict_seeds": (C.c_int, [C.POINTER(Camera), P, P, C.c_size_t, C.c_int32, C.c_int32, P, P]),
+    "rsvio_predict_seeds_d": (C.c_int, [C.POINTER(Camera), P, P, C.c_size_t, C.c_int32, C.c_int32, P, P, P]),
+    "rsvio_track_points_seeded": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int32, P, P, C.c_int32, C.c_int32,
+                                            C.c_float, P, P]),
+    "rsvio_tracker_set_prediction": (C.c_int, [P, C.POINTER(TrackPrediction)]),
+    "rsvio_tracker_prediction_report": (C.c_int, [P, C.POINTER(PredictionCounts), P, C.c_size_t, P, C.c_size_t]),
     # diagnostic (not in the header): the frame end's whole gate on two given maps, in place
     "rsvio_dbg_stereo_gate_frame": (C.c_int, [C.POINTER(StereoGate), C.c_int32, C.c_int32, P, P, P,
                                               C.POINTER(C.c_size_t), P, P, P, C.POINTER(C.c_size_t), P, P,

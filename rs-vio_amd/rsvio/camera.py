@@ -72,6 +72,21 @@ class Camera:
         cs = self.struct()
         check(_lib.load().rsvio_unproject_d(C.byref(cs), d_px, n, d_out, d_valid, stream))
 
+    def project(self, pts):
+        """n x 3 camera-frame points -> (n x 2 f64 pixels, valid bool); NaN where invalid
+        (rsvio_project: EUCM den <= 0, radtan Z <= 0)."""
+        pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+        out = np.zeros((len(pts), 2), np.float64)
+        valid = np.zeros(len(pts), np.uint8)
+        cs = self.struct()
+        check(_lib.load().rsvio_project(C.byref(cs), ptr(pts), len(pts), ptr(out), ptr(valid)))
+        return out, valid.astype(bool)
+
+    def project_device(self, d_pts: int, n: int, d_out: int, d_valid: int | None, stream: int | None = None):
+        """rsvio_project_d: enqueue on device pointers (no synchronisation)."""
+        cs = self.struct()
+        check(_lib.load().rsvio_project_d(C.byref(cs), d_pts, n, d_out, d_valid, stream))
+
 
 # EuRoC cam0/cam1 (config/euroc_vio.yaml:11-17) and TUM-VI EUCM (config/tum_vi.yaml:11-17)
 EUROC = (Camera.from_config([458.654, 457.296, 367.215, 248.375],

@@ -43,6 +43,7 @@ class FrameResult:
     ba_iterations: int | None = None    # LM iterations of the window's solve (the retry's, after a fallback)
     pose_covariance: np.ndarray | None = None   # Estimator(pose_covariance=True): 6x6 of T_W_B when pnp_status > 0
     n_gate_rejected: int | None = None   # Estimator(stereo_gate=...): pairs the tracker's gate dropped; None: off
+    n_seeded: tuple | None = None        # Estimator(predict=...): (left, right) entries tracked from a predicted seed; None: off
 
 
 @dataclass
@@ -137,6 +138,14 @@ class DeviceBackend:
         """The collected frame's gate counters (they came back with its lists)."""
         return self.tracker.gate_counts()
 
+    def set_prediction(self, R_l, R_r):
+        """The rotation hints R_cur_prev of both cameras for the next frame submitted (None: none)."""
+        self.tracker.set_prediction(R_l, R_r)
+
+    def prediction_counts(self):
+        """The collected frame's seeded / unseeded counters."""
+        return self.tracker.prediction_counts()
+
     def close(self):
         for o in (self.tracker, self.motion, self.solver, self._ba_stream):
             o.close()
@@ -152,7 +161,7 @@ class Estimator:
                  translation_threshold: float = 0.05, rotation_threshold: float = 0.05, device: int = 0,
                  backend=None, pipelined: bool = False, landmark_init: str = "ray", gate=None, cull: bool = False,
                  robust_motion=None, drop_outliers: bool = False, pose_covariance: bool = False,
-                 stereo_gate: StereoGateConfig | None = None):
+                 stereo_gate: StereoGateConfig | None = None, predict: str | None = None):
         # robust_motion: a rsvio.motion.RansacConfig -- the frame's pose and keyframe flag come from
         # MotionTracker.track_motion_tracker_robust (a stereo 3-point RANSAC, the LM on its
         # consensus set) instead of the plain LM over every joined observation; None: the
@@ -190,6 +199,18 @@ class Estimator:
             from .tracker import StereoGate
             self.backend.set_stereo_gate(StereoGate(stereo_gate.mode, stereo_gate.max_error,
                                                     np.linalg.inv(self.T_B_Cl) @ self.T_B_Cr))
+        # predict: the tracker starts every feature's LK search where a rotation hint says its bearing
+        # went (rsvio_tracker_set_prediction).  "external": the caller passes delta_R_B = R_Bcur_Bprev
+        # (e.g. an integrated gyro) with each frame; "constant_velocity": the last inter-frame body
+        # rotation R_W_B(t-1)^T R_W_B(t-2), when both earlier frames have a successful PnP pose
+        # (otherwise the frame is not predicted).  Per camera R_c = R_C_B delta_R_B R_B_C.
+        # FrameResult.n_seeded counts the seeded entries; None: the reference's tracker
+        if predict not in (None, "external", "constant_velocity"):
+            raise ValueError('predict must be None, "external" or "constant_velocity"')
+        if predict is not None and not hasattr(self.backend, "set_prediction"):
+            raise ValueError("predict needs a backend with set_prediction (the device tracker)")
+        self.predict = predict
+        self._pnp_R = [None, None]   # R_W_B of frames t-2, t-1 where their PnP succeeded
         self.frame_id = 0
         self._map_key = None
         self._tcb_key = None
@@ -220,28 +241,71 @@ class Estimator:
             self._tcb_key = key
         return self._tcb
 
-    def process_frame(self, left: np.ndarray, right: np.ndarray) -> FrameResult:
+    def process_frame(self, left: np.ndarray, right: np.ndarray, delta_R_B=None) -> FrameResult:
+        """delta_R_B (predict="external"): R_Bcur_Bprev, the body rotation since the last frame; None:
+        this frame is not predicted."""
+        self._set_prediction(delta_R_B)
         return self._process_tracked(self._tracked(self.backend.track(left, right)))
 
+    def _set_prediction(self, delta_R_B):
+        """The hint of the frame about to be submitted, as the per-camera rotations of the tracker."""
+        if self.predict is None:
+            if delta_R_B is not None:
+                raise ValueError('delta_R_B needs Estimator(predict="external")')
+            return
+        if self.predict == "constant_velocity":
+            if delta_R_B is not None:
+                raise ValueError('delta_R_B needs Estimator(predict="external")')
+            R2, R1 = self._pnp_R
+            delta_R_B = None if R1 is None or R2 is None else R1.T @ R2
+        if delta_R_B is None:
+            self.backend.set_prediction(None, None)
+            return
+        d = np.asarray(delta_R_B, np.float64)
+        if d.shape != (3, 3):
+            raise ValueError("delta_R_B must be 3 x 3")
+        R_B_Cl, R_B_Cr = self.T_B_Cl[:3, :3], self.T_B_Cr[:3, :3]
+        self.backend.set_prediction(R_B_Cl.T @ d @ R_B_Cl, R_B_Cr.T @ d @ R_B_Cr)
+
     def _tracked(self, feats):
-        """A collected frame's features with its gate count, taken before the next frame is submitted."""
-        return feats, (None if self.stereo_gate is None else int(self.backend.gate_counts().n_rejected))
+        """A collected frame's features with its gate and prediction counts, taken before the next frame
+        is submitted."""
+        n_seeded = None if self.predict is None else tuple(self.backend.prediction_counts().n_seeded)
+        return feats, (None if self.stereo_gate is None else int(self.backend.gate_counts().n_rejected)), n_seeded
 
     def run(self, frames):
         """process_frame over an iterable of (left, right) image pairs, yielding one FrameResult
         per frame, with the tracker one frame ahead (module docstring): frame t + 1 is submitted
         right after frame t's features are collected, before frame t's motion tracking and BA.
         In pipelined mode a keyframe's FrameResult gets its BA outcome when the solve is next
-        waited for (at the latest by flush()); frames left unconsumed are collected on exit."""
+        waited for (at the latest by flush()); frames left unconsumed are collected on exit.
+        predict="external": (left, right, delta_R_B) triples.  predict="constant_velocity" is refused:
+        frame t + 1 is submitted before frame t's pose, which its hint needs, is known."""
+        if self.predict == "constant_velocity":
+            raise ValueError('run() submits frame t + 1 before frame t\'s pose is known: predict="constant_velocity" '
+                             "needs process_frame")
+        return self._run(frames)
+
+    def _run(self, frames):
         if self.drop_outliers:  # a frame's outliers leave the tracker before the next one is submitted
-            for left, right in frames:
-                yield self.process_frame(left, right)
+            for f in frames:
+                yield self.process_frame(*f)
             return
+
+        def submit(f):
+            # predict="external": (left, right, delta_R_B) triples; the hint is host state of the
+            # tracker and applies to this submit alone
+            if self.predict == "external":
+                self._set_prediction(f[2] if len(f) > 2 else None)
+            elif len(f) > 2:
+                raise ValueError('(left, right, delta_R_B) frames need Estimator(predict="external")')
+            self.backend.submit(f[0], f[1])
+
         it = iter(frames)
         nxt = next(it, None)
         if nxt is None:
             return
-        self.backend.submit(*nxt)
+        submit(nxt)
         in_flight = True
         try:
             while in_flight:
@@ -249,7 +313,7 @@ class Estimator:
                 in_flight = False
                 nxt = next(it, None)
                 if nxt is not None:
-                    self.backend.submit(*nxt)
+                    submit(nxt)
                     in_flight = True
                 yield self._process_tracked(feats)
         finally:
@@ -259,7 +323,7 @@ class Estimator:
     def _process_tracked(self, feats) -> FrameResult:
         """Steps 2-3 of process_frame (estimator.rs:195-248) for a frame whose features are in."""
         self.frame_id += 1
-        ((ids_l, uv_l), (ids_r, uv_r)), n_gate_rejected = feats
+        ((ids_l, uv_l), (ids_r, uv_r)), n_gate_rejected, n_seeded = feats
         frame = Frame(frame_id=self.frame_id, T_W_B=np.eye(4), T_B_Cl=self.T_B_Cl, T_B_Cr=self.T_B_Cr,
                       is_keyframe=True, left_features=(ids_l, uv_l), right_features=(ids_r, uv_r))
         pnp_status = pnp_iters = pnp_cost = pose_cov = None
@@ -292,6 +356,9 @@ class Estimator:
             if status > 0:
                 frame.T_W_B = T_W_B
                 frame.is_keyframe = bool(is_kf)
+        if self.predict == "constant_velocity":  # the last two frames' rotations, where PnP gave one
+            ok = pnp_status is not None and pnp_status > 0
+            self._pnp_R = [self._pnp_R[1], np.array(frame.T_W_B[:3, :3], np.float64) if ok else None]
         ba_status = ba_iters = None
         pending = False
         if frame.is_keyframe:
@@ -306,7 +373,8 @@ class Estimator:
                     ba_iters = None if r is None else int(r.iterations)
         out = FrameResult(self.frame_id, frame.is_keyframe, frame.T_W_B.copy(), len(ids_l), len(ids_r),
                           pnp_status, ba_status, pnp_iterations=pnp_iters, pnp_cost=pnp_cost,
-                          ba_iterations=ba_iters, pose_covariance=pose_cov, n_gate_rejected=n_gate_rejected)
+                          ba_iterations=ba_iters, pose_covariance=pose_cov, n_gate_rejected=n_gate_rejected,
+                          n_seeded=n_seeded)
         if pending:
             self._pending_frame = (out, frame)
         return out
@@ -354,7 +422,9 @@ class NativeEstimator:
                     ("ba_wait", C.c_double), ("total", C.c_double), ("n_solves", C.c_int32),
                     ("ba_iterations", C.c_int32), ("fallbacks", C.c_int32), ("reserved", C.c_int32)]
 
-    def __init__(self, backend: DeviceBackend, T_B_Cl, T_B_Cr, window: int = 10):
+    def __init__(self, backend: DeviceBackend, T_B_Cl, T_B_Cr, window: int = 10, predict=None):
+        if predict is not None:  # motion-predicted tracking is an option of the Python Estimator only
+            raise ValueError("NativeEstimator does not predict: predict must be None (use Estimator)")
         from . import _lib
         from .ba import fallback_cfg, lm_cfg
         from .motion import pnp_cfg

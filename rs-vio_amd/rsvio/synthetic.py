@@ -725,6 +725,68 @@ def euroc_scene_stream(n_frames: int, w: int = 752, h: int = 480, step: float = 
     return SceneStream(frames=frames, T_W_B=poses, T_B_Cl=T_B_CL.copy(), T_B_Cr=T_B_CR.copy(), intrinsics=intr)
 
 
+def rot_y(a: float) -> np.ndarray:
+    c, s = math.cos(a), math.sin(a)
+    return np.array([[c, 0.0, s], [0.0, 1.0, 0.0], [-s, 0.0, c]])
+
+
+@dataclass
+class RotatingPair:
+    """Two stereo frames of the config-4 scene between which each camera yaws about its own y axis."""
+    frames: list            # [(left0, right0), (left1, right1)] u8 h x w
+    R_cur_prev: np.ndarray  # the rotation hint of either camera: Ry(theta)^T
+    intrinsics: tuple       # (cam0, cam1) radtan parameters (fx, fy, cx, cy, k1, k2, p1, p2)
+    theta_deg: float
+
+
+def rotating_scene_pair(theta_deg: float, w: int = 376, h: int = 240, seed: int = 4, noise: float = 2.0) -> RotatingPair:
+    """The fixture of motion-predicted tracking: the scene of euroc_scene_stream seen from T_B_CL /
+    T_B_CR (frame 0) and from the same poses with their rotation multiplied on the right by a yaw
+    Ry(theta) about the camera's y axis (frame 1) -- a pure rotation about each camera's centre, so the
+    hint R_cur_prev = Ry(theta)^T predicts every pixel exactly.  Noise: `noise` * N(0, 1) from
+    default_rng(1) for frame 0 and default_rng(2) for frame 1 (left image first), rint, clip to u8."""
+    _, intr, T, bands, rays = _scene_setup(2, w, h, 0.02, seed)
+    Ry = rot_y(math.radians(theta_deg))
+    frames = []
+    for t in range(2):
+        rng = np.random.default_rng(1 + t)
+        pair = []
+        for c, T_B_C in enumerate((T_B_CL, T_B_CR)):
+            T_W_C = T_B_C.copy()
+            if t == 1:
+                T_W_C[:3, :3] = T_W_C[:3, :3] @ Ry
+            img = _scene_image(_NumpyOps, T, bands, rays[c], T_W_C)
+            img = img + noise * rng.standard_normal((h, w))
+            pair.append(np.clip(np.rint(img), 0, 255).astype(np.uint8))
+        frames.append(tuple(pair))
+    return RotatingPair(frames=frames, R_cur_prev=Ry.T.copy(), intrinsics=intr, theta_deg=theta_deg)
+
+
+def rotating_scene_stream(n_frames: int, theta_deg: float, w: int = 376, h: int = 240, seed: int = 4,
+                          noise: float = 2.0):
+    """A yawing stereo sequence for the Estimator's prediction: the rig of euroc_scene_stream turning
+    about the body origin, each frame by the body rotation that is a yaw Ry(theta) about the left
+    camera's y axis.  Returns (SceneStream, delta_R_B) with delta_R_B = R_Bcur_Bprev, the same exact
+    hint between any two consecutive frames."""
+    rng, intr, T, bands, rays = _scene_setup(n_frames, w, h, 0.02, seed)
+    R_B_C = T_B_CL[:3, :3]
+    step_B = R_B_C @ rot_y(math.radians(theta_deg)) @ R_B_C.T   # R_Bprev_Bcur
+    frames, poses = [], []
+    T_W_B = np.eye(4)
+    for t in range(n_frames):
+        poses.append(T_W_B.copy())
+        pair = []
+        for c, T_B_C in enumerate((T_B_CL, T_B_CR)):
+            img = _scene_image(_NumpyOps, T, bands, rays[c], T_W_B @ T_B_C)
+            img = img + noise * rng.standard_normal((h, w))
+            pair.append(np.clip(np.rint(img), 0, 255).astype(np.uint8))
+        frames.append(tuple(pair))
+        T_W_B = T_W_B.copy()
+        T_W_B[:3, :3] = T_W_B[:3, :3] @ step_B
+    stream = SceneStream(frames=frames, T_W_B=poses, T_B_Cl=T_B_CL.copy(), T_B_Cr=T_B_CR.copy(), intrinsics=intr)
+    return stream, step_B.T.copy()
+
+
 def euroc_scene_stream_device(n_frames: int, device, w: int = 752, h: int = 480, step: float = 0.02, seed: int = 4,
                               noise: float = 2.0) -> SceneStream:
     """euroc_scene_stream rendered with torch on `device` (bench input generation: 500 frames in

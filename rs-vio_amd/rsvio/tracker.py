@@ -51,6 +51,37 @@ def track_points(pyr0: np.ndarray, pyr1: np.ndarray, w: int, h: int, levels: int
     return out, valid.astype(bool)
 
 
+def track_points_seeded(pyr0: np.ndarray, pyr1: np.ndarray, w: int, h: int, levels: int, aff: np.ndarray,
+                        seeds: np.ndarray, max_iterations: int = 20, thresh: float = 0.01):
+    """rsvio_track_points_seeded: track_points with feature i's search started at seeds[i] (n x 2 f32
+    pixels of the second image; a non-finite seed: its own position); returns (aff_out, valid)."""
+    aff = np.ascontiguousarray(aff, np.float32).reshape(-1, 6)
+    seeds = np.ascontiguousarray(seeds, np.float32).reshape(-1, 2)
+    n = aff.shape[0]
+    if len(seeds) != n:
+        raise ValueError("one seed per feature")
+    out = np.empty_like(aff)
+    valid = np.zeros(n, np.uint8)
+    check(_lib.load().rsvio_track_points_seeded(ptr(pyr0), ptr(pyr1), w, h, levels, ptr(aff), ptr(seeds), n,
+                                                max_iterations, C.c_float(thresh), ptr(out), ptr(valid)))
+    return out, valid.astype(bool)
+
+
+def predict_seeds(camera, R, px, w: int, h: int):
+    """rsvio_predict_seeds: where the bearings of n pixels (n x 2 f32) of `camera` (rsvio.camera.Camera)
+    land after the rotation R = R_cur_prev (3 x 3), as pixels of a w x h image; (seeds n x 2 f32,
+    seeded bool) -- an entry that is not seeded keeps its own pixel."""
+    px = np.ascontiguousarray(px, np.float32).reshape(-1, 2)
+    R = np.ascontiguousarray(R, np.float64)
+    if R.size != 9:
+        raise ValueError("R must be 3 x 3")
+    seeds = np.zeros_like(px)
+    seeded = np.zeros(len(px), np.uint8)
+    cs = camera.struct()
+    check(_lib.load().rsvio_predict_seeds(C.byref(cs), ptr(R), ptr(px), len(px), w, h, ptr(seeds), ptr(seeded)))
+    return seeds, seeded.astype(bool)
+
+
 def detect_key_points(img: np.ndarray, grid_size: int, existing_xy: np.ndarray | None = None, cap: int = 4096):
     """New corners (k x 2 u32) and their FAST scores in the reference's cell scan order."""
     img = np.ascontiguousarray(img, np.uint8)
@@ -94,6 +125,14 @@ class GateCounts:
     n_pairs: int = 0      # ids in both cameras' maps before the gate
     n_rejected: int = 0   # of them, the ones the gate dropped
     n_invalid: int = 0    # of those, the ones without a bearing (a failed unprojection, RAY with s < 0)
+
+
+@dataclass
+class PredictionCounts:
+    """rsvio_prediction_counts: per camera (left, right), the entries of the previous frame's lists
+    whose search started at a predicted seed, and those that fell back to their own position."""
+    n_seeded: tuple = (0, 0)
+    n_unseeded: tuple = (0, 0)
 
 
 def stereo_gate_lists(gate: StereoGate, convention_l, convention_r, ids_l, uv_l, ids_r, uv_r):
@@ -247,6 +286,39 @@ class StereoPatchTracker:
         if c.n_rejected:
             check(_lib.load().rsvio_tracker_gate_report(self._h, None, ptr(ids), ptr(err), len(ids), C.byref(n)))
         return c, ids, err
+
+    def set_prediction(self, R_l, R_r=None):
+        """rsvio_tracker_set_prediction: the rotation hints R_cur_prev (3 x 3) of the left and right
+        camera for exactly the next frame enqueued (process_frame, or submit); set_prediction(None)
+        clears a pending one.  Needs set_cameras."""
+        if R_l is None:
+            check(_lib.load().rsvio_tracker_set_prediction(self._h, None))
+            return
+        p = _lib.TrackPrediction()
+        for name, R in (("R_l", R_l), ("R_r", R_r)):
+            R = np.asarray(R, np.float64)
+            if R.shape != (3, 3):
+                raise ValueError(f"{name} must be 3 x 3")
+            getattr(p, name)[:] = R.reshape(9).tolist()
+        check(_lib.load().rsvio_tracker_set_prediction(self._h, C.byref(p)))
+
+    def prediction_report(self):
+        """rsvio_tracker_prediction_report of the last collected frame: (PredictionCounts, seeds_l,
+        seeds_r) -- the seeds (k x 2 f32) in the order of the previous frame's lists; zeros and empty
+        when that frame had no prediction."""
+        c = _lib.PredictionCounts()
+        check(_lib.load().rsvio_tracker_prediction_report(self._h, C.byref(c), None, 0, None, 0))
+        n = [c.n_seeded[k] + c.n_unseeded[k] for k in range(2)]
+        sl, sr = np.zeros((n[0], 2), np.float32), np.zeros((n[1], 2), np.float32)
+        if n[0] + n[1]:
+            check(_lib.load().rsvio_tracker_prediction_report(self._h, None, ptr(sl), n[0], ptr(sr), n[1]))
+        return PredictionCounts(tuple(c.n_seeded), tuple(c.n_unseeded)), sl, sr
+
+    def prediction_counts(self) -> "PredictionCounts":
+        """The counters of prediction_report() alone."""
+        c = _lib.PredictionCounts()
+        check(_lib.load().rsvio_tracker_prediction_report(self._h, C.byref(c), None, 0, None, 0))
+        return PredictionCounts(tuple(c.n_seeded), tuple(c.n_unseeded))
 
     def remove_id(self, ids):
         """StereoPatchTracker::remove_id (feature_tracker.rs:201-206): the device lists are

@@ -87,6 +87,8 @@ GROUPS = {
                                   "frame's lists on the device",
     "rsvio_tracker_set_stereo_gate": "stereo gate: the epipolar check on every frame's pairs (state of a handle), "
                                      "its report, and the same check on two given lists",
+    "rsvio_predict_seeds": "motion-predicted tracking: the LK search started where a rotation hint says a feature "
+                           "went (seeds, the handle's one-frame prediction and its report)",
 }
 
 
