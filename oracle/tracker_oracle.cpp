@@ -86,7 +86,12 @@ struct Img {
 };
 
 // image_utilities.rs:75-80
+// A level narrower than r has no in-bound pixel.  There `width - r` underflows in the reference
+// (a panic in a checked build; wrapped, every x >= r passes and the pixel access behind it
+// panics), so it never returns a result that this answer contradicts; unguarded, the wrap made
+// set_data_jac_se2 read outside the level (far outside for a far-away point).
 inline bool inbound(const Img& im, float x, float y, uint32_t r) {
+    if (im.w < r || im.h < r) return false;
     uint32_t xi = sat_u32(std::round(x));
     uint32_t yi = sat_u32(std::round(y));
     return xi >= r && yi >= r && xi < im.w - r && yi < im.h - r;

@@ -1311,6 +1311,26 @@ int rsvio_build_pyramid(const uint8_t* img, int32_t w, int32_t h, int32_t levels
     });
 }
 
+// Diagnostic (tests; not in the header): what PyramidPlan::init decides for a w x h image and
+// `levels` levels -- the output tile of every level (entries at and past `levels`, and entry 0,
+// are zero), the mask of the levels whose vertical taps are read from HBM, and the dynamic LDS of
+// the launch -- so that a test knows which path of pyramid_kernel its shape took.
+int rsvio_dbg_pyramid_plan(int32_t w, int32_t h, int32_t levels, int32_t* tile_w, int32_t* tile_h, uint32_t* direct,
+                           uint64_t* lds_bytes) {
+    if (!tile_w || !tile_h || !direct || !lds_bytes) return RSVIO_ERR_INVALID_ARG;
+    return guarded([&] {
+        rsvio::PyramidPlan plan;
+        plan.init(w, h, levels);
+        for (int i = 0; i < rsvio::kMaxLevels; ++i) {
+            tile_w[i] = plan.launch.tile_w[i];
+            tile_h[i] = plan.launch.tile_h[i];
+        }
+        *direct = plan.launch.direct;
+        *lds_bytes = (uint64_t)plan.lds_bytes;
+        return (int)RSVIO_OK;
+    });
+}
+
 int rsvio_track_points(const uint8_t* pyr0, const uint8_t* pyr1, int32_t w, int32_t h, int32_t levels,
                        const float* aff_in, int32_t n, int32_t max_iterations, float thresh, float* aff_out,
                        uint8_t* valid_out) {

@@ -264,6 +264,9 @@ SIG = {
     "rsvio_dbg_stereo_gate_frame": (C.c_int, [C.POINTER(StereoGate), C.c_int32, C.c_int32, P, P, P,
                                               C.POINTER(C.c_size_t), P, P, P, C.POINTER(C.c_size_t), P, P,
                                               C.POINTER(GateCounts)]),
+    # diagnostic (not in the header): PyramidPlan::init's tiles, HBM-tap level mask and dynamic LDS
+    "rsvio_dbg_pyramid_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, P, P, C.POINTER(C.c_uint32),
+                                         C.POINTER(C.c_uint64)]),
     "rsvio_pyramid_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "rsvio_build_pyramid": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, P]),
     "rsvio_track_points": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int32, C.c_int32, C.c_float,

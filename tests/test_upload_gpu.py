@@ -15,6 +15,12 @@ def _stream(torch):
     return torch.cuda.Stream(device=0)
 
 
+def _after_fills(torch, s):
+    """torch fills a tensor on its current stream, which a new (non-blocking) stream does not wait
+    for: order the stream's next work after it, or a late fill overwrites the copy."""
+    s.wait_stream(torch.cuda.current_stream(0))
+
+
 @pytest.mark.parametrize("nbytes", [0, 1, 7, 8, 9, 4096 + 5, 752 * 480 * 2, 3 * 1024 * 1024 + 3])
 def test_pinned_source_bytes_equal(gpu, nbytes):
     import torch
@@ -24,6 +30,7 @@ def test_pinned_source_bytes_equal(gpu, nbytes):
     src = torch.from_numpy(rng.integers(0, 256, max(nbytes, 1), dtype=np.uint8)).pin_memory()
     dst = torch.full((max(nbytes, 1) + 64,), 0xA5, dtype=torch.uint8, device="cuda:0")
     s = _stream(torch)
+    _after_fills(torch, s)
     _lib.check(lib.rsvio_upload_async(dst.data_ptr(), src.data_ptr(), nbytes, s.cuda_stream))
     s.synchronize()
     got = dst.cpu().numpy()
@@ -39,11 +46,13 @@ def test_pageable_source_and_unaligned_destination_fall_back(gpu):
     host = rng.integers(0, 256, 100_003, dtype=np.uint8)  # pageable numpy memory
     dst = torch.zeros(100_003 + 64, dtype=torch.uint8, device="cuda:0")
     s = _stream(torch)
+    _after_fills(torch, s)
     _lib.check(lib.rsvio_upload_async(dst.data_ptr(), host.ctypes.data, host.size, s.cuda_stream))
     s.synchronize()
     assert np.array_equal(dst.cpu().numpy()[:host.size], host)
     pinned = torch.from_numpy(host).pin_memory()
     dst.zero_()
+    _after_fills(torch, s)
     _lib.check(lib.rsvio_upload_async(dst.data_ptr() + 1, pinned.data_ptr(), host.size, s.cuda_stream))
     s.synchronize()
     got = dst.cpu().numpy()
