@@ -629,24 +629,25 @@ std::vector<Corner> local_maxima(const std::vector<Corner>& ts, uint32_t r) {
     std::stable_sort(o.begin(), o.end(), [](const Corner& a, const Corner& b) {
         return a.y < b.y || (a.y == b.y && a.x < b.x);
     });
-    const uint32_t height = o.empty() ? 0 : o.back().y;
-    std::vector<std::vector<const Corner*>> rows(height + 1);
-    for (const auto& t : o) rows[t.y].push_back(&t);
+    // A tracked feature rounds to any u32 (a NaN or far-off position saturates), so nothing here
+    // may be sized by `height`, and the window arithmetic is 64-bit: rows [lo, hi) are a range of
+    // the sorted list.
+    const uint64_t height = o.empty() ? 0 : o.back().y;
+    const uint64_t R = r;
     std::vector<Corner> out;
     for (const auto& t : o) {
-        const uint32_t cx = t.x, cy = t.y;
+        const uint64_t cx = t.x, cy = t.y;
         const float cs = t.score;
         bool is_max = true;
-        const uint32_t lo = r > cy ? 0 : cy - r;
-        const uint32_t hi = cy + r + 1 > height ? height : cy + r + 1;
-        for (uint32_t y = lo; y < hi && is_max; ++y)
-            for (const Corner* c : rows[y]) {
-                if (c->x + r < cx) continue;
-                if (c->x > cx + r) break;
-                if (c->score > cs) { is_max = false; break; }
-                if (c->score < cs) continue;
-                if (c->y < cy || (c->y == cy && c->x < cx)) { is_max = false; break; }
-            }
+        const uint64_t lo = R > cy ? 0 : cy - R;
+        const uint64_t hi = cy + R + 1 > height ? height : cy + R + 1;
+        auto it = std::lower_bound(o.begin(), o.end(), lo, [](const Corner& c, uint64_t y) { return c.y < y; });
+        for (; it != o.end() && it->y < hi; ++it) {
+            if ((uint64_t)it->x + R < cx || (uint64_t)it->x > cx + R) continue;
+            if (it->score > cs) { is_max = false; break; }
+            if (it->score < cs) continue;
+            if (it->y < cy || (it->y == cy && it->x < cx)) { is_max = false; break; }
+        }
         if (is_max) out.push_back(t);
     }
     return out;
